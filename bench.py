@@ -15,7 +15,10 @@ children's status); started under torchrun it is one rank.  WORLD_SIZE must equa
 `--verify-dp` checks, before timing, that the N-rank averaged gradients equal the single-process
 gradients on the concatenated batch.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel by share of step time
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times K steps and prints it (`value`, `ms_per_step`; `roofline`
+null); `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy.  `--full` adds every other figure
+and check below: the per-kernel probes, the sustained leg, the CPU baseline, the scaling prediction and, with more than one
+rank, the default data-parallel check and the no-communication leg.  `roofline` is for the dominant kernel by share of step time
 (round 2: wino6_pair16p_kernel -- the data-gradient plane GEMMs of a Winograd F(6x6,3x3)
 residual-block layer as persistent workgroups + its 64 transform-domain weight-gradient planes in one
 grid, 12 launches per step; `roofline_other` lists the other MFMA kernels): EXECUTED FLOPs
@@ -40,6 +43,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "nir-gan_amd"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
@@ -382,6 +386,41 @@ def verify_dp(a, dev, rank, world, reducer, netG, netD, make_trainer, rgb, nir, 
     return res
 
 
+DUMP_BYTES = 64_000_000            # --dump-outputs: all files together, headers included
+
+
+def step_outputs(loss_view, pl_losses, trainer, netG, netD) -> dict:
+    """What one step hands its caller, on the host: the loss scalars (float64), the generator's prediction for the batch (fused path) and
+    both networks' parameters after the Adam steps, each network's floating-point state_dict entries flattened and concatenated in key order."""
+    out = {}
+    if pl_losses is not None:
+        out["loss_D"] = np.float64(float(pl_losses[0]))
+        out["loss_G"] = np.float64(float(pl_losses[1]))
+    else:
+        out.update({k: np.float64(v) for k, v in loss_view.as_dict().items()})
+    if trainer is not None:
+        out["pred"] = trainer.pred.detach().to("cpu", torch.float32, copy=True).numpy()       # (a copy also on the CPU test seam)
+    for name, net in (("netG_params", netG), ("netD_params", netD)):
+        vals = [v.detach().float().reshape(-1) for v in net.state_dict().values() if v.is_floating_point()]
+        out[name] = torch.cat(vals).cpu().numpy()
+    return out
+
+
+def write_outputs(d: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array.  Over DUMP_BYTES in all, each array of more than 2^20 elements is cut to a fixed sample (indices
+    drawn with seed 0, sorted; the same for the same length in every run) written as <name>_sample.npy."""
+    os.makedirs(d, exist_ok=True)
+    big = sum(v.nbytes for v in arrays.values() if v.size > 1 << 20)
+    small = sum(v.nbytes for v in arrays.values()) - big
+    budget = DUMP_BYTES - 256 * len(arrays) - small
+    keep = 1.0 if small + big + 256 * len(arrays) <= DUMP_BYTES else budget / big
+    for name, v in arrays.items():
+        if keep < 1.0 and v.size > 1 << 20:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, int(v.size * keep), replace=False))
+            v, name = v.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
 class Tick:
     """A HIP event on the launch stream, or a host timestamp on the CPU test seam (same elapsed_time interface, ms)."""
 
@@ -439,7 +478,20 @@ def main():
     ap.add_argument("--emulate-cpu", action="store_true",
                     help="TEST SEAM (tests/test_bench_launch.py): gloo + the numpy emulator of the C ABI instead of RCCL + the HIP "
                          "library, to exercise launching / sharding / verification without a GPU; the numbers mean nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel roofline probes, matrix-pipe share, generator forward / backward "
+                         "figures, the sustained leg, the CPU baseline, the scaling prediction and, with more than one rank, the default "
+                         "data-parallel check and the no-communication leg.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (losses, generator prediction, both networks' "
+                         "parameters after the Adam steps) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_probe = a.no_cpu_baseline = True
+        a.sustain = 0.0
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -497,9 +549,9 @@ def main():
                               inject=inject, reducer=red, precision=a.precision, micro_batches=a.micro)
     rgb, nir = synth(a.bs, a.size, a.size, 1234 + rank, dev)
     dp_check = None
-    # the first real multi-GPU run checks itself: with more than one rank the gradient check runs unless switched off (mixed-resolution
-    # ranks hold different shapes: no concatenated batch to compare with)
-    auto_verify = reducer is not None and world > 1 and not a.no_verify_dp and not a.mixed
+    # the first real multi-GPU run checks itself: under --full with more than one rank the gradient check runs unless switched off
+    # (mixed-resolution ranks hold different shapes: no concatenated batch to compare with)
+    auto_verify = a.full and reducer is not None and world > 1 and not a.no_verify_dp and not a.mixed
     if a.verify_dp or auto_verify:
         if reducer is None:
             sys.exit("bench.py: --verify-dp needs more than one rank (or NIRGAN_FORCE_DIST=1)")
@@ -598,9 +650,7 @@ def main():
         tr._prepare(a.bs, a.size, a.size)        # the probes bracket the middle (256x256) bucket's launches
     if pl_model is not None:
         a.no_probe = True               # the autograd bridge leases its own engines: per-kernel figures come from the fused run
-        kinds, plans = {}, []
-    else:
-        kinds, plans = mfma_probes(tr)
+    kinds, plans = ({}, []) if a.no_probe else mfma_probes(tr)
     # generator-forward MFMA utilisation (second half of BASELINE.json's metric): HIP events around the generator's
     # forward plan inside the timed steps (the launch stream is torch's current stream)
     gen_fwd_events, gen_bwd_events = [], []
@@ -657,9 +707,9 @@ def main():
     t0 = time.perf_counter()
     for _ in range(a.steps):
         if a.mixed:
-            tr.step(rgb, nir, True)
+            last = tr.step(rgb, nir, True)
         else:
-            tr.step(rgb, nir)
+            last = tr.step(rgb, nir)
     barrier()
     dt = time.perf_counter() - t0
     rank_ms, comm_ms = [dt / a.steps * 1e3], None
@@ -674,11 +724,16 @@ def main():
         rank_ms = [round(float(x[0]), 3) for x in allt]
         comm_ms = [round(float(x[1]), 4) for x in allt]
         dt = max(float(x[0]) for x in allt) * a.steps / 1e3          # MAX over ranks
+    # what the last timed step handed its caller, taken before any --full leg steps the networks again
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = step_outputs(last, pl_step.last if pl_model is not None else None, tr if pl_model is None else None,
+                              pl_model.netG if pl_model is not None else netG, pl_model.netD if pl_model is not None else netD)
     # ---- the same steps WITHOUT the collectives, in this process on this rank's own shard (a second trainer with no reducer): what the
     # step costs when nothing is exchanged -- measured here instead of taken from another run, so that `measured - no_comm` is this
     # node's communication cost and the `predicted` line has its own one-GPU input
     nocomm_ms = None
-    if reducer is not None and world > 1 and pl_model is None and not a.mixed and a.micro == 1:
+    if a.full and reducer is not None and world > 1 and pl_model is None and not a.mixed and a.micro == 1:
         try:
             solo = make_trainer(None)
             for _ in range(2):
@@ -756,12 +811,14 @@ def main():
                      "vs_burst": round((a.bs * world * n_chunks * chunk / wall) / (a.bs * world * a.steps / dt), 4),
                      "note": "steps issued back to back after the timed ones; chunks of 10 steps between HIP events on the launch stream "
                              "(rank 0's own clock; the headline `value` stays the barrier-bracketed K steps)"}
-    out_l = tr.step(rgb, nir)
+    out_l = tr.step(rgb, nir) if a.full else last
     if pl_model is not None:
         losses = {"loss_D": float(pl_step.last[0]), "loss_G": float(pl_step.last[1])}
     else:
         losses = out_l.as_dict()
     assert all(v == v and abs(v) < 1e30 for v in losses.values()), f"non-finite losses {losses}"
+    if dumped is not None:
+        write_outputs(a.dump_outputs, dumped)
 
     if rank == 0:
         ms = dt / a.steps * 1e3
@@ -899,7 +956,7 @@ def main():
             out["ms_per_step_no_comm_by_rank"] = nocomm_ms
         elif nocomm_ms is not None:
             out["ms_per_step_no_comm_by_rank"] = nocomm_ms
-        if pl_model is None and not a.mixed and a.micro == 1 and not a.emulate_cpu:
+        if a.full and pl_model is None and not a.mixed and a.micro == 1 and not a.emulate_cpu:
             try:
                 # (N > 1: the model's one-GPU input is THIS run's no-communication leg, not the N-rank time)
                 ms1 = ms if world == 1 else (min(nocomm_ms) if isinstance(nocomm_ms, list) else min(rank_ms))
