@@ -114,7 +114,7 @@ typedef struct {
     /* kernel choice where more than one applies (A/B measurements, tests): 0 = default -- problems with both operands stored as bf16,
      * N % 256 == 0, run % 64 == 0 and rounds of 256 x 256 tiles that fill at least 62 % of the CUs run on the 256 x 256 x 64 eight-phase tile (one workgroup of
      * eight waves per CU, LDS-DMA in flight across the barriers), everything else on the 128-row tile; NIRGAN_CONV_TILE128 = always the
-     * 128-row tile; NIRGAN_CONV_TILE256 = the 256-wide tile also for exact-fp32 problems.  Results differ by fp32 summation order only. */
+     * 128-row tile (results differ by fp32 summation order only); NIRGAN_CONV_X3_R4 as below.  Any other value fails with NIRGAN_ERR_ARG. */
     int algo;
     /* precision 3 -- fp32-EQUIVALENT on the bf16 matrix pipe (round 5): every fp32 operand is split into three bf16 terms h + m + l (exact)
      * and a product is contracted as the six bf16 products down to 2^-16 of the leading one (dropped: <= 2^-24 |a b|), fp32 accumulate;
@@ -136,9 +136,7 @@ typedef struct {
     int out_span;
 } nirgan_conv_desc;
 #define NIRGAN_CONV_TILE128 1
-#define NIRGAN_CONV_X3_BN64 3   /* precision 3: the 256 x 64 block tile also where 256 x 128 applies (A/B) */
 #define NIRGAN_CONV_X3_R4 4     /* precision 3, N % 128 == 0: the four-wave register-fed tile of igemm_x3r.h instead of the eight-wave tile (A/B; same output bits) */
-#define NIRGAN_CONV_TILE256 2   /* exact-fp32 problems (N % 256 == 0, run % 32 == 0, >= 128 tiles) on the 256-wide tile too (A/B: within 1 % of the 128-row tile) */
 
 int nirgan_conv_igemm(const nirgan_conv_desc* d, void* stream);
 
@@ -168,10 +166,10 @@ typedef struct {
     int pq_bf16;                          /* 1: p and q point to bf16 twins (same geometry; the producers' out_bf16 / dy_bf16);
                                            * precision 1, N > 64, and N, run, p_cs, q_cs multiples of 8 */
     int algo;                             /* kernel choice where more than one applies (A/B measurements, tests): 0 = default (plane-matrix
-                                           * problems walk their units as persistent workgroups); NIRGAN_WGRAD_ONE_UNIT = one unit per workgroup */
+                                           * problems walk their units as persistent workgroups); NIRGAN_WGRAD_ONE_UNIT = one unit per workgroup;
+                                           * NIRGAN_WGRAD_TILE128 as below.  Any other value fails with NIRGAN_ERR_ARG. */
 } nirgan_wgrad_desc;
 #define NIRGAN_WGRAD_ONE_UNIT 1
-#define NIRGAN_WGRAD_RING10 3    /* the 256-wide tile with an LDS ring of 10 half-tile slots (160 KB) instead of 8 (128 KB): A/B, no gain measured */
 #define NIRGAN_WGRAD_TILE128 2   /* bf16 twins: never the 256 x 256 x 64 eight-phase tile (persistent workgroups, one per CU), which is the
                                   * default for N % 256 == 0, ntaps * run % 256 == 0, OW % 64 == 0 or 64 % OW == 0, rows_per_split % 64 == 0 */
 
@@ -568,9 +566,10 @@ typedef struct {
     float* fuse_gz; float* fuse_part; int64_t fuse_part_elems; int fuse_act; float fuse_slope;
     int algo;                             /* plane-GEMM kernel choice (nirgan_wino6_gemm, nirgan_wino6_gemm_wgrad_pair) where more than one
                                              applies: 0 = default (persistent workgroups on 32-k stages for C = 256 / 512);
-                                             NIRGAN_W6_ONE_TILE = one tile per workgroup (16-k stages); NIRGAN_W6_PERSIST16 = persistent workgroups
-                                             on 16-k stages; NIRGAN_W6_DIRECT_TILE = the direct convolution tile (32-k stages, one tile per
-                                             workgroup).  All compute the same products; kept for A/B measurements and the kernel tests. */
+                                             NIRGAN_W6_ONE_TILE = one tile per workgroup (16-k stages); NIRGAN_W6_DIRECT_TILE = the direct
+                                             convolution tile (32-k stages, one tile per workgroup); NIRGAN_W6_X3_R4, NIRGAN_W6_PATCH_PER_* as
+                                             below.  All compute the same products; kept for A/B measurements and the kernel tests.  Any other
+                                             value fails with NIRGAN_ERR_ARG (the transforms check the field too). */
     const void* U3;                       /* optional (precision 3, as nirgan_conv_desc.w_x3): U as three bf16 planes h, m, l, each [planes][K][C],
                                              written by nirgan_wino6_weights_x3 next to U.  With it (and C % 32 == 0, K % 64 == 0) the plane
                                              GEMMs run on the bf16 matrix pipe as six bf16 products per fp32 product, V split inside the
@@ -580,9 +579,7 @@ typedef struct {
                                              launches (the weight-gradient planes take nirgan_wgrad_desc.precision = 3 on their own). */
 } nirgan_wino6_desc;
 #define NIRGAN_W6_ONE_TILE 1
-#define NIRGAN_W6_PERSIST16 2
 #define NIRGAN_W6_DIRECT_TILE 3
-#define NIRGAN_W6_TILE256 4                 /* nirgan_wino6_gemm: the exact-fp32 256 x 256 eight-phase tile as persistent workgroups (A/B; K % 256 == 0, C % 32 == 0) */
 #define NIRGAN_W6_X3_R4 5                   /* nirgan_wino6_gemm with U3, K % 128 == 0: the plane GEMMs on the four-wave register-fed split tile (A/B; same bits) */
 #define NIRGAN_W6_PATCH_PER_THREAD 16      /* nirgan_wino6_input*: F(6x6,3x3) patches one per thread (A/B; default for the plain / dY transforms: a wave per patch x 32 channels) */
 #define NIRGAN_W6_PATCH_PER_LANES 17       /* ... and the lane-spread form also for the normalising variant (default there: one per thread) */

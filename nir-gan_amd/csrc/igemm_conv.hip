@@ -28,10 +28,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ng::ConvParams
 }
 
 // the bf16 operand mode's 256 x 256 x 64 eight-phase tile (igemm_tile256.h): one workgroup of eight waves per CU
-template <bool F32>
 __global__ __launch_bounds__(512, 2) void conv_igemm256_kernel(const ng::ConvParams p) {
     __shared__ __attribute__((aligned(16))) char lds[ng::T256_LDS];
-    ng::conv_tile256<F32>(p, ng_xcd_remap(blockIdx.x, gridDim.x), lds);
+    ng::conv_tile256(p, ng_xcd_remap(blockIdx.x, gridDim.x), lds);
 }
 
 // precision 3 (igemm_x3.h): fp32 operands as three bf16 terms, six bf16 products -- 256 x BN x 32 tiles walked by persistent workgroups,
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(512, 2) void conv_x3_kernel(const ng::X3Work w) {
 }
 
 // the same arithmetic as ONE wave per SIMD (igemm_x3r.h): four waves, wave tile 64 x BN, the activation operand split in registers and
-// never staged, the weight planes through a four-stage LDS-DMA ring, the epilogue's slices under the item's last K-tile
+// never staged, the weight planes through two LDS stages fed from registers, the epilogue's slices under the item's last K-tile
 template <int BN, int KIND>
 __global__ __launch_bounds__(256, 1) void conv_x3r_kernel(const ng::X3Work w) {
     __shared__ __attribute__((aligned(1024))) char ring[ng::X3R<BN>::RING];
@@ -170,22 +169,46 @@ int ng::ng_launch_conv_x3(const ng::ConvParams* ps, const int n, const int bn, c
         w.spread = 1;
     }
     const dim3 grid(total < G ? total : G);
+    switch (ng::conv_x3_route(ps, n, bn)) {
+        case ng::X3R_GENERIC: hipLaunchKernelGGL((conv_x3r_kernel<128, 2>), grid, dim3(256), 0, st, w); break;
+        case ng::X3R_STATS: hipLaunchKernelGGL((conv_x3r_kernel<128, 1>), grid, dim3(256), 0, st, w); break;
+        case ng::X3R_PLAIN: hipLaunchKernelGGL((conv_x3r_kernel<128, 0>), grid, dim3(256), 0, st, w); break;
+        case ng::X3_N128: hipLaunchKernelGGL(conv_x3_kernel<128>, grid, dim3(512), 0, st, w); break;
+        case ng::X3_N64: hipLaunchKernelGGL(conv_x3_kernel<64>, grid, dim3(512), 0, st, w); break;
+    }
+    return nirgan_check_launch(what);
+}
+
+ng::X3Kernel ng::conv_x3_route(const ng::ConvParams* ps, const int n, const int bn) {
     bool reg_fed = true, gen = false, stats = false;
     for (int i = 0; i < n; ++i) {
         reg_fed = reg_fed && ng::conv_x3r_ok(ps[i], bn);
         gen = gen || ng::conv_x3r_generic(ps[i]);
         stats = stats || ng::conv_x3r_stats(ps[i]);
     }
-    if (reg_fed && gen) hipLaunchKernelGGL((conv_x3r_kernel<128, 2>), grid, dim3(256), 0, st, w);
-    else if (reg_fed && stats) hipLaunchKernelGGL((conv_x3r_kernel<128, 1>), grid, dim3(256), 0, st, w);
-    else if (reg_fed) hipLaunchKernelGGL((conv_x3r_kernel<128, 0>), grid, dim3(256), 0, st, w);
-    else if (bn == 128) hipLaunchKernelGGL(conv_x3_kernel<128>, grid, dim3(512), 0, st, w);
-    else hipLaunchKernelGGL(conv_x3_kernel<64>, grid, dim3(512), 0, st, w);
-    return nirgan_check_launch(what);
+    if (reg_fed) return gen ? ng::X3R_GENERIC : (stats ? ng::X3R_STATS : ng::X3R_PLAIN);
+    return bn == 128 ? ng::X3_N128 : ng::X3_N64;
 }
-static int launch_conv_x3(const ng::ConvParams* ps, const int n, const int bn, hipStream_t st, const char* what) {
-    return ng::ng_launch_conv_x3(ps, n, bn, 1, 0, 0, 0, st, what);
+
+// Which kernel a convolution launch of 1..4 problems runs on (one place: the launchers and the name query read it).  Precision 3
+// takes the three-term split tile where it covers every problem of the launch (one tile width for all); what it does not cover runs
+// as exact fp32.  A single problem's launch may take the 256-wide tile of the bf16 operand mode; a group never does.
+enum ConvKernel { CONV_K_X3R, CONV_K_X3_N128, CONV_K_X3_N64, CONV_K_TILE256, CONV_K_TILE128, CONV_K_TILE64 };
+static const char* const CONV_KERNEL_NAMES[] = {"conv_x3r_kernel<128>", "conv_x3_kernel<128>", "conv_x3_kernel<64>", "conv_igemm256_kernel",
+                                                "conv_igemm_kernel<128>", "conv_igemm_kernel<64>"};
+struct ConvRoute { ConvKernel k; int bn; };          // bn: the split tile's width
+static ConvRoute conv_route(const ng::ConvParams* ps, const int n, const bool group) {
+    bool x3 = ps[0].prec == 3;
+    for (int i = 0; i < n; ++i) x3 = x3 && ng::conv_x3_ok(ps[i]) && (ps[i].N % 128 == 0) == (ps[0].N % 128 == 0);
+    if (x3) {
+        const int bn = ng::conv_x3_bn(ps, n, ng_cu_count_conv());
+        const ng::X3Kernel k = ng::conv_x3_route(ps, n, bn);
+        return {k == ng::X3_N128 ? CONV_K_X3_N128 : (k == ng::X3_N64 ? CONV_K_X3_N64 : CONV_K_X3R), bn};
+    }
+    if (!group && ps[0].algo != NIRGAN_CONV_TILE128 && ng::conv_tile256_ok(ps[0])) return {CONV_K_TILE256, 0};
+    return {ps[0].N > 64 ? CONV_K_TILE128 : CONV_K_TILE64, 0};
 }
+static bool conv_route_x3(const ConvRoute& r) { return r.k == CONV_K_X3R || r.k == CONV_K_X3_N128 || r.k == CONV_K_X3_N64; }
 
 #ifdef NG_X3R_STAMP
 extern "C" int nirgan_x3r_stamps(unsigned long long* host, int n) {
@@ -206,32 +229,22 @@ extern "C" int nirgan_conv_igemm(const nirgan_conv_desc* d, void* stream) {
     const int rc = ng::build_conv_params(d, p);
     if (rc != NIRGAN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvRoute r = conv_route(&p, 1, false);
+    if (conv_route_x3(r)) return ng::ng_launch_conv_x3(&p, 1, r.bn, 1, 0, 0, 0, st, "conv_igemm (three-term split tile)");
     if (p.prec == 3) {
-        if (ng::conv_x3_ok(p)) return launch_conv_x3(&p, 1, ng::conv_x3_bn(p, ng_cu_count_conv()), st, "conv_igemm (three-term split tile)");
         NG_REQUIRE(p.ch == p.N, "conv: out_span = 2 needs a problem the three-term split tile covers (run %% 32 == 0, N %% 64 == 0)");
         p.prec = 0;             // what the split tile does not cover runs as exact fp32
     }
-    if (p.algo != NIRGAN_CONV_TILE128 && ng::conv_tile256_ok(p)) {
-        if (p.prec == 0) hipLaunchKernelGGL(conv_igemm256_kernel<true>, dim3(((p.M + 255) >> 8) * (p.N >> 8)), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL(conv_igemm256_kernel<false>, dim3(((p.M + 255) >> 8) * (p.N >> 8)), dim3(512), 0, st, p);
+    if (r.k == CONV_K_TILE256) {
+        hipLaunchKernelGGL(conv_igemm256_kernel, dim3(((p.M + 255) >> 8) * (p.N >> 8)), dim3(512), 0, st, p);
         return nirgan_check_launch("conv_igemm (256 x 256 tile)");
     }
     const dim3 grid(p.mtiles * p.ntiles * p.ksplit);
-#define NG_LAUNCH_CONV(BN, PREC) hipLaunchKernelGGL((conv_igemm_kernel<BN, PREC>), grid, dim3(256), 0, st, p)
-    if (d->N > 64) {
-        if (p.prec == 0) NG_LAUNCH_CONV(128, 0);
-        else if (p.prec == 1 && p.in_bf16) hipLaunchKernelGGL((conv_igemm_kernel<128, 1, true, true>), grid, dim3(256), 0, st, p);
-        else if (p.prec == 1 && p.w_bf16) hipLaunchKernelGGL((conv_igemm_kernel<128, 1, true>), grid, dim3(256), 0, st, p);
-        else if (p.prec == 1) NG_LAUNCH_CONV(128, 1);
-        else NG_LAUNCH_CONV(128, 2);
-    } else {
-        if (p.prec == 0) NG_LAUNCH_CONV(64, 0);
-        else if (p.prec == 1 && p.in_bf16) hipLaunchKernelGGL((conv_igemm_kernel<64, 1, true, true>), grid, dim3(256), 0, st, p);
-        else if (p.prec == 1 && p.w_bf16) hipLaunchKernelGGL((conv_igemm_kernel<64, 1, true>), grid, dim3(256), 0, st, p);
-        else if (p.prec == 1) NG_LAUNCH_CONV(64, 1);
-        else NG_LAUNCH_CONV(64, 2);
-    }
-#undef NG_LAUNCH_CONV
+    ng::conv_tile_form(p, [&](auto form) {
+        using F = decltype(form);
+        if (r.k == CONV_K_TILE128) hipLaunchKernelGGL((conv_igemm_kernel<128, F::prec, F::wb16, F::ab16>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((conv_igemm_kernel<64, F::prec, F::wb16, F::ab16>), grid, dim3(256), 0, st, p);
+    });
     if (p.ksplit > 1) {
         const long long total = (long long)p.M * (p.N / 4);
         const int grid = int((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
@@ -243,15 +256,7 @@ extern "C" int nirgan_conv_igemm(const nirgan_conv_desc* d, void* stream) {
 extern "C" const char* nirgan_conv_kernel_name(const nirgan_conv_desc* d) {
     ng::ConvParams p;
     if (ng::build_conv_params(d, p) != NIRGAN_OK) return nullptr;
-    if (p.prec == 3) {
-        if (ng::conv_x3_ok(p)) {
-            const int bn = ng::conv_x3_bn(p, ng_cu_count_conv());
-            return ng::conv_x3r_ok(p, bn) ? "conv_x3r_kernel<128>" : (bn == 128 ? "conv_x3_kernel<128>" : "conv_x3_kernel<64>");
-        }
-        p.prec = 0;
-    }
-    if (p.algo != NIRGAN_CONV_TILE128 && ng::conv_tile256_ok(p)) return p.prec == 0 ? "conv_igemm256_kernel<fp32>" : "conv_igemm256_kernel";
-    return d->N > 64 ? "conv_igemm_kernel<128>" : "conv_igemm_kernel<64>";
+    return CONV_KERNEL_NAMES[conv_route(&p, 1, false).k];
 }
 
 extern "C" int nirgan_conv_igemm_group(const nirgan_conv_desc* const* descs, int n, void* stream) {
@@ -272,17 +277,10 @@ extern "C" int nirgan_conv_igemm_group(const nirgan_conv_desc* const* descs, int
         total += g.p[i].mtiles * g.p[i].ntiles;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // the three-term split tile for every problem of the group, or exact fp32 for all of them
+    const ConvRoute r = conv_route(g.p, n, true);
+    if (conv_route_x3(r)) return ng::ng_launch_conv_x3(g.p, n, r.bn, 1, 0, 0, 0, st, "conv_igemm_group (three-term split tile)");
     if (g.p[0].prec == 3) {
-        // the three-term split tile for every problem of the group, or exact fp32 for all of them
-        bool ok = true;
-        for (int i = 0; i < n; ++i) ok = ok && ng::conv_x3_ok(g.p[i]) && (g.p[i].N % 128 == 0) == (g.p[0].N % 128 == 0);
-        if (ok) {
-            // (the tile width from the whole group's tile count: the phases of one launch share the chip)
-            long long t128 = 0;
-            for (int i = 0; i < n; ++i) t128 += g.p[i].N % 128 == 0 ? ng::conv_x3_tiles(g.p[i], 128) : 0;
-            const int bn = (g.p[0].N % 128 != 0 || g.p[0].algo == NIRGAN_CONV_X3_BN64 || t128 * 4 < 3ll * ng_cu_count_conv()) ? 64 : 128;
-            return launch_conv_x3(g.p, n, bn, st, "conv_igemm_group (three-term split tile)");
-        }
         for (int i = 0; i < n; ++i) {
             NG_REQUIRE(g.p[i].ch == g.p[i].N, "conv_igemm_group: out_span = 2 needs problems the three-term split tile covers (run %% 32 == 0, N %% 64 == 0, one tile width)");
             g.p[i].prec = 0;
@@ -291,22 +289,10 @@ extern "C" int nirgan_conv_igemm_group(const nirgan_conv_desc* const* descs, int
     for (int i = n; i < 4; ++i) { g.p[i] = g.p[0]; g.first[i] = 0x7fffffff; }
     g.first[4] = total;
     g.n = n;
-    const int prec = g.p[0].prec;
-#define NG_LAUNCH_GROUP(BN, PREC) hipLaunchKernelGGL((conv_group_kernel<BN, PREC>), dim3(total), dim3(256), 0, st, g)
-    const bool wb = g.p[0].w_bf16 != 0, ab = g.p[0].in_bf16 != 0;
-    if (wide) {
-        if (prec == 0) NG_LAUNCH_GROUP(128, 0);
-        else if (prec == 1 && ab) hipLaunchKernelGGL((conv_group_kernel<128, 1, true, true>), dim3(total), dim3(256), 0, st, g);
-        else if (prec == 1 && wb) hipLaunchKernelGGL((conv_group_kernel<128, 1, true>), dim3(total), dim3(256), 0, st, g);
-        else if (prec == 1) NG_LAUNCH_GROUP(128, 1);
-        else NG_LAUNCH_GROUP(128, 2);
-    } else {
-        if (prec == 0) NG_LAUNCH_GROUP(64, 0);
-        else if (prec == 1 && ab) hipLaunchKernelGGL((conv_group_kernel<64, 1, true, true>), dim3(total), dim3(256), 0, st, g);
-        else if (prec == 1 && wb) hipLaunchKernelGGL((conv_group_kernel<64, 1, true>), dim3(total), dim3(256), 0, st, g);
-        else if (prec == 1) NG_LAUNCH_GROUP(64, 1);
-        else NG_LAUNCH_GROUP(64, 2);
-    }
-#undef NG_LAUNCH_GROUP
+    ng::conv_tile_form(g.p[0], [&](auto form) {
+        using F = decltype(form);
+        if (r.k == CONV_K_TILE128) hipLaunchKernelGGL((conv_group_kernel<128, F::prec, F::wb16, F::ab16>), dim3(total), dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((conv_group_kernel<64, F::prec, F::wb16, F::ab16>), dim3(total), dim3(256), 0, st, g);
+    });
     return nirgan_check_launch("conv_igemm_group");
 }

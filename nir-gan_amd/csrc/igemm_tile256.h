@@ -26,7 +26,6 @@ namespace ng {
 
 constexpr int T256_HALF = 128 * 128;          // bytes of one half-tile image
 constexpr int T256_LDS = 8 * T256_HALF;       // 128 KB: the ring of 8 slots (and the epilogue's 8 wave-private staging areas)
-constexpr int T256_LDS10 = 10 * T256_HALF;    // 160 KB: the ring of 10 slots
 
 __device__ __forceinline__ void t256_bar() {
     __builtin_amdgcn_sched_barrier(0);
@@ -40,28 +39,26 @@ __device__ __forceinline__ void t256_bar() {
 // register set `which`), mma(i, j) waits for them and accumulates quadrant (i, j) from the A registers and B set j.
 //
 // The half-tiles of the K loop form ONE sequence h = 4 k + {0: B half 0, 1: A half 0, 2: B half 1, 3: A half 1} of K-tile k, and the
-// LDS holds a ring of S slots of 16 KB, half h in slot h mod S.  Global phase g = 4 k + part does three things:
+// LDS holds a ring of T256_SLOTS = 8 slots of 16 KB, half h in slot h mod 8.  Global phase g = 4 k + part does three things:
 //     fragment reads of half g + 1            (part 0: A half 0, 1: B half 1, 2: A half 1, 3: B half 0 of K-tile k + 1)
 //     16 MFMAs of quadrant part               (C00 = A0 B0, C01 = A0 B1, C10 = A1 B0, C11 = A1 B1)
-//     LDS-DMA of half g + S - 1 into the slot that half g - 1 left two phases ago, then vmcnt(2 (S - 3)): all but the S - 3 youngest
+//     LDS-DMA of half g + 7 into the slot that half g - 1 left two phases ago, then vmcnt(10): all but the five youngest
 //     halves have landed, i.e. half g + 2 -- read in the NEXT phase
-// Every slot lives one ring period: issued, retired by the wait S - 3 phases later, read in the phase after that, restaged two phases
-// after the read.  S = 8 (128 KB) keeps five halves in flight, S = 10 (all 160 KB of a CU's LDS) seven.  The weight-gradient tile
-// streams every operand byte from beyond L2 once (the convolution tile re-reads its patch nine times from L2) and takes 3 010 cycles
-// per K-tile against 2 690 with the operands pinned in L2 (profiles/r04_tile256_stamps.txt) -- but NOT for want of prefetch distance:
-// the ring of 10 measures 3 039 (profiles/r04_tile256_ring10.txt).  What the farther operand costs is the ISSUE of the LDS-DMA pieces
-// (the load segment's length), not the wait for them: the CU's outstanding-request capacity, not the ring, bounds what is in flight.
-// The slot numbers are literals: the loop is unrolled over lcm(4, S) phases (2 K-tiles for S = 8, 5 for S = 10).  The fragment reads are
-// spread 2 : 1 : 2 : 1 over the phases; the first form of this loop (round 4, first day) read A half 0 and B half 0 together and waited
-// vmcnt(6) once per K-tile.  In the last K-tiles, where fewer than S - 3 younger halves exist, the waits drain (vmcnt(0)).
-template <int S> __device__ __forceinline__ void t256_wait_ring() {
-    static_assert(S == 8 || S == 10, "ring of 8 or 10 half-tile slots");
-    if constexpr (S == 8) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-}
+// Every slot lives one ring period: issued, retired by the wait five phases later, read in the phase after that, restaged two phases
+// after the read.  The weight-gradient tile streams every operand byte from beyond L2 once (the convolution tile re-reads its patch
+// nine times from L2) and takes 3 010 cycles per K-tile against 2 690 with the operands pinned in L2 (profiles/r04_tile256_stamps.txt)
+// -- but NOT for want of prefetch distance: a ring of 10 slots (all 160 KB of a CU's LDS, seven halves in flight) measured 3 039
+// (profiles/r04_tile256_ring10.txt).  What the farther operand costs is the ISSUE of the LDS-DMA pieces (the load segment's length),
+// not the wait for them: the CU's outstanding-request capacity, not the ring, bounds what is in flight.
+// The slot numbers are literals: the loop is unrolled over 8 phases (2 K-tiles).  The fragment reads are spread 2 : 1 : 2 : 1 over the
+// phases; the first form of this loop (round 4, first day) read A half 0 and B half 0 together and waited vmcnt(6) once per K-tile.
+// In the last K-tiles, where fewer than five younger halves exist, the waits drain (vmcnt(0)).
+constexpr int T256_SLOTS = 8;
+__device__ __forceinline__ void t256_wait_ring() { asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); }
 
-template <int S, int G, class IA, class IB, class ADV, class RA, class RB, class MMA>
+template <int G, class IA, class IB, class ADV, class RA, class RB, class MMA>
 __device__ __forceinline__ void t256_phase(const int k, const int nk, IA& issueA, IB& issueB, ADV& advance, RA& readA, RB& readB, MMA& mma) {
+    constexpr int S = T256_SLOTS;
     constexpr int part = G & 3;
     constexpr int jr = (G + 1) & 3, sr = (G + 1) % S;                  // the half whose fragments this phase reads: type, slot
     constexpr int ji = (G + S - 1) & 3, si = (G + S - 1) % S;          // the half this phase stages
@@ -79,7 +76,7 @@ __device__ __forceinline__ void t256_phase(const int k, const int nk, IA& issueA
         else if constexpr (ji == 1) issueA(si, 0);
         else if constexpr (ji == 2) issueB(si, 1);
         else { issueA(si, 1); advance(); }
-        t256_wait_ring<S>();
+        t256_wait_ring();
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -89,51 +86,48 @@ __device__ __forceinline__ void t256_phase(const int k, const int nk, IA& issueA
 }
 
 // K-tiles KT .. of one unrolled period; returns when the K-tiles run out
-template <int S, int KT, class IA, class IB, class ADV, class RA, class RB, class MMA>
+template <int KT, class IA, class IB, class ADV, class RA, class RB, class MMA>
 __device__ __forceinline__ void t256_period(const int k0, const int nk, IA& issueA, IB& issueB, ADV& advance, RA& readA, RB& readB, MMA& mma) {
-    constexpr int KTS = (S == 8 ? 8 : 20) / 4;
-    if constexpr (KT < KTS) {
+    if constexpr (KT < T256_SLOTS / 4) {
         if (k0 + KT >= nk) return;
-        t256_phase<S, 4 * KT + 0>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
-        t256_phase<S, 4 * KT + 1>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
-        t256_phase<S, 4 * KT + 2>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
-        t256_phase<S, 4 * KT + 3>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
-        t256_period<S, KT + 1>(k0, nk, issueA, issueB, advance, readA, readB, mma);
+        t256_phase<4 * KT + 0>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
+        t256_phase<4 * KT + 1>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
+        t256_phase<4 * KT + 2>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
+        t256_phase<4 * KT + 3>(k0 + KT, nk, issueA, issueB, advance, readA, readB, mma);
+        t256_period<KT + 1>(k0, nk, issueA, issueB, advance, readA, readB, mma);
     }
 }
 
-template <int S, int H, class IA, class IB, class ADV>
+template <int H, class IA, class IB, class ADV>
 __device__ __forceinline__ void t256_prologue_issue(const int nk, IA& issueA, IB& issueB, ADV& advance) {
-    if constexpr (H < S - 1) {
+    if constexpr (H < T256_SLOTS - 1) {
         if ((H >> 2) < nk) {
             if constexpr ((H & 3) == 0) issueB(H, 0);
             else if constexpr ((H & 3) == 1) issueA(H, 0);
             else if constexpr ((H & 3) == 2) issueB(H, 1);
             else { issueA(H, 1); advance(); }
         }
-        t256_prologue_issue<S, H + 1>(nk, issueA, issueB, advance);
+        t256_prologue_issue<H + 1>(nk, issueA, issueB, advance);
     }
 }
 
-template <int S, class IA, class IB, class ADV, class RA, class RB, class MMA>
+template <class IA, class IB, class ADV, class RA, class RB, class MMA>
 __device__ __forceinline__ void t256_kloop(const int nk, const int wr, IA&& issueA, IB&& issueB, ADV&& advance, RA&& readA, RB&& readB, MMA&& mma) {
-    // prologue: halves 0 .. S - 2, then "phase -1": the fragment reads of half 0 (B half 0 of K-tile 0)
-    t256_prologue_issue<S, 0>(nk, issueA, issueB, advance);
-    const bool full = 4 * nk >= S - 1;        // all S - 1 halves exist: the counted waits apply
+    // prologue: halves 0 .. 6, then "phase -1": the fragment reads of half 0 (B half 0 of K-tile 0)
+    t256_prologue_issue<0>(nk, issueA, issueB, advance);
+    const bool full = 4 * nk >= T256_SLOTS - 1;       // all seven halves exist: the counted waits apply
     if (full) {
-        if constexpr (S == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");      // half 0: all but the S - 2 younger ones
-        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");      // half 0: all but the six younger ones
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     t256_bar();                               // ... from every wave
     if (wr == 1) t256_bar();                  // the stagger: waves 4-7 run one barrier behind from here on
     readB(0, 0);
-    if (full) t256_wait_ring<S>();            // half 1
+    if (full) t256_wait_ring();               // half 1
     t256_bar();
     t256_bar();                               // (the empty MFMA segment of that phase: keeps the two wave groups half a phase apart)
-    constexpr int KTS = (S == 8 ? 8 : 20) / 4;
-    for (int k0 = 0; k0 < nk; k0 += KTS) t256_period<S, 0>(k0, nk, issueA, issueB, advance, readA, readB, mma);
+    for (int k0 = 0; k0 < nk; k0 += T256_SLOTS / 4) t256_period<0>(k0, nk, issueA, issueB, advance, readA, readB, mma);
     if (wr == 0) t256_bar();                  // waves 0-3 wait for the staggered half: every fragment read and every DMA is done
 }
 
@@ -144,19 +138,12 @@ __device__ __forceinline__ void t256_kloop(const int nk, const int wr, IA&& issu
 #define T256_STAMP(i)
 #endif
 
-// F32 = true: the SAME structure in exact fp32 (v_mfma_f32_32x32x2_f32, the parity path's arithmetic): a K-tile is 32 k (the 128-byte
-// rows hold 32 floats), a phase is 2 x 1 tiles of 32 x 32 x 16 k-steps of 2 = 32 MFMAs of 64 cycles, so the load segment of the partner
-// wave (the same LDS-DMA pieces and fragment reads as in bf16) hides under 2 048 instead of 256 cycles of matrix work.  Fragments as in
-// conv_tile: one ds_read_b128 hands a lane 4 consecutive k of its row, lanes 0-31 chunk 2g, lanes 32-63 chunk 2g + 1, MFMA j of group g
-// contracts k = 8g + j and 8g + 4 + j.  `in_base / w_base / out_base`: base overrides for plane-batched launches (csrc/wino6.hip).
-template <bool F32 = false, int S = 8>
-__device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, char* lds,
-                                             const float* in_base = nullptr, const float* w_base = nullptr, float* out_base = nullptr) {
-    const float* const p_in = in_base ? in_base : p.in;
-    const float* const p_w = w_base ? w_base : p.w;
-    float* const p_out = out_base ? out_base : p.out;
-    constexpr int ES = F32 ? 4 : 2;             // bytes per operand element
-    constexpr int KT = F32 ? 32 : 64;           // k per K-tile (one 128-byte row)
+__device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, char* lds) {
+    const float* const p_in = p.in;             // (read up front: where the kernarg loads sit shapes the schedule)
+    const float* const p_w = p.w;
+    float* const p_out = p.out;
+    constexpr int ES = 2;                       // bytes per operand element
+    constexpr int KT = 64;                      // k per K-tile (one 128-byte row)
     constexpr int CW = 16 / ES;                 // elements per 16-byte chunk
 #ifdef NG_DIAG256
     unsigned long long ng_t[8];
@@ -221,89 +208,46 @@ __device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, 
     const int b_rd0 = (wc * 32 + (lane & 15)) * 128 + x0, b_rd1 = (wc * 32 + (lane & 15)) * 128 + x1;
     bf16x8 A[4][2], B0[2][2], B1[2][2];
     f32x4 acc[2][2][4][2];
-    // fp32: rows wr * 64 + mt * 32 + (lane & 31) of an A half, wc * 32 + (lane & 31) of a B half; group g reads chunk 2g + half
-    const int half = lane >> 5, keyf = (lane >> 1) & 7;
-    int f_rd[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) f_rd[g] = (lane & 31) * 128 + (((2 * g + half) ^ keyf) << 4);
-    f32x4 Af[2][4], B0f[4], B1f[4];
-    f32x16 accF[2][2][2];
-    if constexpr (F32) {
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) accF[i][j][mt][r] = 0.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[i][j][mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+                for (int nt = 0; nt < 2; ++nt) acc[i][j][mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto readA = [&](const int slot) {
         const char* s = lds + slot * T256_HALF;
-        if constexpr (F32) {
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) Af[mt][g] = *reinterpret_cast<const f32x4*>(s + (wr * 64 + mt * 32) * 128 + f_rd[g]);
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                A[mt][0] = *reinterpret_cast<const bf16x8*>(s + a_rd0 + mt * 2048);
-                A[mt][1] = *reinterpret_cast<const bf16x8*>(s + a_rd1 + mt * 2048);
-            }
+        for (int mt = 0; mt < 4; ++mt) {
+            A[mt][0] = *reinterpret_cast<const bf16x8*>(s + a_rd0 + mt * 2048);
+            A[mt][1] = *reinterpret_cast<const bf16x8*>(s + a_rd1 + mt * 2048);
         }
     };
     auto readB = [&](const int which, const int slot) {
         const char* s = lds + slot * T256_HALF;
-        if constexpr (F32) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s + (wc * 32) * 128 + f_rd[g]);
-                if (which == 0) B0f[g] = v; else B1f[g] = v;
-            }
-        } else {
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const bf16x8 v0 = *reinterpret_cast<const bf16x8*>(s + b_rd0 + nt * 2048), v1 = *reinterpret_cast<const bf16x8*>(s + b_rd1 + nt * 2048);
-                if (which == 0) { B0[nt][0] = v0; B0[nt][1] = v1; } else { B1[nt][0] = v0; B1[nt][1] = v1; }
-            }
+        for (int nt = 0; nt < 2; ++nt) {
+            const bf16x8 v0 = *reinterpret_cast<const bf16x8*>(s + b_rd0 + nt * 2048), v1 = *reinterpret_cast<const bf16x8*>(s + b_rd1 + nt * 2048);
+            if (which == 0) { B0[nt][0] = v0; B0[nt][1] = v1; } else { B1[nt][0] = v0; B1[nt][1] = v1; }
         }
     };
     auto mma = [&](const int i, const int j) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
-        if constexpr (F32) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
+        for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
+            for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                        accF[i][j][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Af[mt][g][q], j == 0 ? B0f[g][q] : B1f[g][q], accF[i][j][mt], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-                        acc[i][j][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[mt][s], j == 0 ? B0[nt][s] : B1[nt][s], acc[i][j][mt][nt], 0, 0, 0);
-        }
+                for (int nt = 0; nt < 2; ++nt)
+                    acc[i][j][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[mt][s], j == 0 ? B0[nt][s] : B1[nt][s], acc[i][j][mt][nt], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     };
 
     T256_STAMP(1)
-    t256_kloop<S>(nk, wr, issueA, issueB, advance, readA, readB,
+    t256_kloop(nk, wr, issueA, issueB, advance, readA, readB,
                [&](const int i, const int j) {         // (i, j are literals at every call site: the branches fold after inlining)
                    if (i == 0 && j == 0) mma(0, 0); else if (i == 0) mma(0, 1); else if (j == 0) mma(1, 0); else mma(1, 1);
                });
@@ -322,35 +266,22 @@ __device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, 
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
-                        if (F32 && nt == 1) continue;             // fp32: one 32-column tile per (i, j), a column on lanes l and l + 32
-                        float k0, s1 = 0.f, s2 = 0.f;
-                        if constexpr (F32) {
-                            k0 = __shfl(accF[i][j][0][0], lane & 31, 64);
+                        const float k0 = __shfl(acc[i][j][0][nt][0], lane & 15, 64);
+                        float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-                            for (int mt = 0; mt < 2; ++mt)
+                        for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-                                for (int r = 0; r < 16; ++r) {
-                                    const float v = accF[i][j][mt][r] - k0;
-                                    s1 += v;
-                                    s2 += v * v;
-                                }
-                        } else {
-                            k0 = __shfl(acc[i][j][0][nt][0], lane & 15, 64);
-#pragma unroll
-                            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const float v = acc[i][j][mt][nt][r] - k0;
-                                    s1 += v;
-                                    s2 += v * v;
-                                }
-                            s1 += __shfl_xor(s1, 16, 64);
-                            s2 += __shfl_xor(s2, 16, 64);
-                        }
+                            for (int r = 0; r < 4; ++r) {
+                                const float v = acc[i][j][mt][nt][r] - k0;
+                                s1 += v;
+                                s2 += v * v;
+                            }
+                        s1 += __shfl_xor(s1, 16, 64);
+                        s2 += __shfl_xor(s2, 16, 64);
                         s1 += __shfl_xor(s1, 32, 64);
                         s2 += __shfl_xor(s2, 32, 64);
-                        const int col = n0 + wc * 64 + j * 32 + (F32 ? (lane & 31) : nt * 16 + (lane & 15));
-                        if (lane < (F32 ? 32 : 16) && col < p.N) {
+                        const int col = n0 + wc * 64 + j * 32 + (nt * 16 + (lane & 15));
+                        if (lane < 16 && col < p.N) {
                             sp[col] = k0;
                             sp[p.N + col] = s1;
                             sp[2 * p.N + col] = s2;
@@ -446,25 +377,15 @@ __device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, 
     };
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        if constexpr (F32) {                 // C/D of v_mfma_f32_32x32x2_f32: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
+            for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        stg[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 64 + j * 32 + (lane & 31)] = accF[i][j][mt][r];
-        } else {
+                for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            stg[(mt * 16 + (lane >> 4) * 4 + r) * 64 + j * 32 + nt * 16 + (lane & 15)] = acc[i][j][mt][nt][r];
-        }
+                    for (int r = 0; r < 4; ++r)
+                        stg[(mt * 16 + (lane >> 4) * 4 + r) * 64 + j * 32 + nt * 16 + (lane & 15)] = acc[i][j][mt][nt][r];
         if (p.out16) half_out(i, std::integral_constant<int, 8>{});
         else half_out(i, std::integral_constant<int, 4>{});
     }
@@ -488,7 +409,6 @@ __device__ __forceinline__ void conv_tile256(const ConvParams& p, const int id, 
 // 8 distinct 32-byte bank segments.  Q half j, LDS column x holds column j0 + (x >> 5) * 64 + j * 32 + (x & 31) of J (as the
 // convolution tile's B halves).  Host: OW % 64 == 0 or 64 % OW == 0, OH * OW % 64 == 0, rows_per_split % 64 == 0 -- a K-tile is a
 // fixed pattern of pixels relative to its first one, which walks in scalar registers.
-template <int S = 8>
 __device__ __forceinline__ void wgrad_tile256(const WgradParams& p, const int unit, char* lds) {
 #ifdef NG_DIAG256
     unsigned long long ng_t[8];
@@ -574,7 +494,7 @@ __device__ __forceinline__ void wgrad_tile256(const WgradParams& p, const int un
     // register-only and would otherwise be hoisted over it), and only THEN joins the two 8-byte halves of an operand -- any register
     // copy the join needs happens after the data has arrived.  Offsets are 16-bit: buffer 1 reads through a second address (+ 64 KB).
     const unsigned lds0 = unsigned(size_t((NG_LDS char*)lds));
-    constexpr int NW = (S * T256_HALF + 65535) / 65536;       // 64 KB windows of the ring (the instruction's offset field has 16 bits)
+    constexpr int NW = (T256_LDS + 65535) / 65536;       // 64 KB windows of the ring (the instruction's offset field has 16 bits)
     unsigned a_adw[4][NW], b_adw[2][NW];
 #pragma unroll
     for (int w_ = 0; w_ < NW; ++w_) {
@@ -637,7 +557,7 @@ __device__ __forceinline__ void wgrad_tile256(const WgradParams& p, const int un
     };
     T256_STAMP(1)
     if (nk > 0)
-        t256_kloop<S>(nk, wr, issueA, issueB, advance, readA, readB,
+        t256_kloop(nk, wr, issueA, issueB, advance, readA, readB,
                       [&](const int i, const int j) { if (j == 0) mma(acc[i][0], B0r); else mma(acc[i][1], B1r); });
 
     T256_STAMP(2)
@@ -689,12 +609,11 @@ inline bool wgrad_tile256_ok(const WgradParams& p) {
 // work; so alone the tile is chosen when its rounds are at least 62 % full (128 tiles on 256 CUs: 55 us against 47; 273 tiles: 120 against
 // 118 -- the fused launch fills such a tail with weight-gradient units and only asks for `pair` = at least half a round).
 inline bool conv_tile256_ok(const ConvParams& p, const bool pair = false, const int cus = 256) {
-    // exact fp32 on this tile only on request (NIRGAN_CONV_TILE256): measured within 1 % of the 128-row tile on long K loops (138.3 against
-    // 136.7 TFLOP/s on the 3x3 256 -> 256 layer, profiles/r04_tile256_fp32_parts.txt) -- at 64 cycles per MFMA the load segment was
-    // never the limit -- so the parity path keeps the kernels its fixtures were measured with
-    const bool b16 = p.prec == 1 && p.in_bf16 && p.w_bf16, f32 = p.prec == 0 && !p.out16 && !p.f_y16 && p.algo == NIRGAN_CONV_TILE256;
-    if (!((b16 || f32) && p.off32 && p.ksplit == 1)) return false;
-    if (p.run % (b16 ? 64 : 32) != 0 || p.N % 256 != 0) return false;
+    // (exact fp32 on an fp32 form of this tile measured within 1 % of the 128-row tile on long K loops -- 138.3 against 136.7 TFLOP/s on
+    // the 3x3 256 -> 256 layer, profiles/r04_tile256_fp32_parts.txt: at 64 cycles per MFMA the load segment was never the limit -- so the
+    // exact path keeps the 128-row tile)
+    if (!(p.prec == 1 && p.in_bf16 && p.w_bf16 && p.off32 && p.ksplit == 1)) return false;
+    if (p.run % 64 != 0 || p.N % 256 != 0) return false;
     // a bf16 output leaves eight channels per lane (16-byte stores, 32-byte loads of bias / mean / rstd, 16-byte loads of a bf16 y): every
     // pixel's channel group must then be 16-byte aligned, as the 128-row tile requires for its eight-channel form
     if (p.out16 && ((p.out_cs | p.out_org | p.out_row | p.out_img) & 7) != 0) return false;

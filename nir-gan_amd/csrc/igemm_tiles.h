@@ -1281,6 +1281,17 @@ __device__ __forceinline__ void wgrad_tile16(const WgradParams& p, const int blo
 }
 
 // ---------------------------------------------------------------- host: descriptor -> parameters
+// The 128-row tile's template arguments <PREC, WB16, AB16> for a problem's precision and operand storage: f(TileForm<...>{}) with the
+// five forms the single, group and pair launches instantiate
+template <int P, bool WB, bool AB> struct TileForm { static constexpr int prec = P; static constexpr bool wb16 = WB, ab16 = AB; };
+template <class F> inline void conv_tile_form(const ConvParams& p, F&& f) {
+    if (p.prec == 0) f(TileForm<0, false, false>{});
+    else if (p.prec == 1 && p.in_bf16) f(TileForm<1, true, true>{});
+    else if (p.prec == 1 && p.w_bf16) f(TileForm<1, true, false>{});
+    else if (p.prec == 1) f(TileForm<1, false, false>{});
+    else f(TileForm<2, false, false>{});
+}
+
 inline int build_conv_params(const nirgan_conv_desc* d, ConvParams& p) {
     NG_REQUIRE(d != nullptr, "conv: null descriptor");
     NG_REQUIRE(d->in && d->w && d->out && d->zero_page, "conv: null pointer");
@@ -1336,6 +1347,8 @@ inline int build_conv_params(const nirgan_conv_desc* d, ConvParams& p) {
     p.in_bf16 = d->in_bf16 ? 1 : 0;
     NG_REQUIRE(!p.in_bf16 || (p.w_bf16 && d->in_cs % 8 == 0), "conv: bf16 activations need bf16-stored weights and in_cs %% 8 == 0 (in_cs=%d)", d->in_cs);
     p.off32 = (d->in_elems * (p.in_bf16 ? 2 : 4) < (int64_t(1) << 32) && d->w_elems * (p.w_bf16 ? 2 : 4) < (int64_t(1) << 32)) ? 1 : 0;
+    NG_REQUIRE(d->algo == 0 || d->algo == NIRGAN_CONV_TILE128 || d->algo == NIRGAN_CONV_X3_R4,
+               "conv: algo=%d (0, NIRGAN_CONV_TILE128 or NIRGAN_CONV_X3_R4)", d->algo);
     p.algo = d->algo;
     p.dbg = nullptr;
     p.ksplit = 1;
@@ -1414,6 +1427,8 @@ inline int build_wgrad_params(const nirgan_wgrad_desc* d, WgradParams& p) {
     p.ntiles_k = (K + 127) / 128;
     p.ntiles_n = d->N > 64 ? (d->N + 127) / 128 : 1;
     NG_REQUIRE(d->precision >= 0 && d->precision <= 3, "wgrad_igemm: precision=%d (0 fp32, 1 bf16, 2 bf16x3, 3 fp32 as three bf16 terms)", d->precision);
+    NG_REQUIRE(d->algo == 0 || d->algo == NIRGAN_WGRAD_ONE_UNIT || d->algo == NIRGAN_WGRAD_TILE128,
+               "wgrad_igemm: algo=%d (0, NIRGAN_WGRAD_ONE_UNIT or NIRGAN_WGRAD_TILE128)", d->algo);
     p.prec = d->precision;
     p.nplanes = d->nplanes > 1 ? d->nplanes : 1;
     p.p_plane = d->p_plane; p.q_plane = d->q_plane;

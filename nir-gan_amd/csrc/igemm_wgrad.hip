@@ -57,35 +57,31 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pair_kernel(const ng::ConvP
 // others the weight-gradient units -- the host divides the CUs so that both kinds finish together (pair256_split): a data gradient over
 // the padded extent of the benchmark layer has 273 tiles, 1.07 rounds of the chip on its own.
 // Between two items of a workgroup one barrier: every wave has read its epilogue staging back before the next item's LDS-DMA lands.
-// S = slots of the weight-gradient tile's LDS ring: 8 = 128 KB (default); 10 = the CU's whole 160 KB, seven half-tiles in flight instead of
-// five (NIRGAN_WGRAD_RING10, A/B: measured 3 039 against 3 014 cycles per K-tile -- the deeper ring buys nothing, profiles/r04_tile256_ring10.txt)
-template <int S>
 __global__ __launch_bounds__(512, 2) void wgrad_igemm256_kernel(const ng::WgradParams p, const int units) {
-    __shared__ __attribute__((aligned(16))) char lds[S * ng::T256_HALF];
+    __shared__ __attribute__((aligned(16))) char lds[ng::T256_LDS];
     bool again = false;
     for (int u = ng_xcd_remap(blockIdx.x, gridDim.x); u < units; u += gridDim.x) {
         if (again) ng::t256_bar();
-        ng::wgrad_tile256<S>(p, u, lds);
+        ng::wgrad_tile256(p, u, lds);
         again = true;
     }
 }
 
-template <int S>
 __global__ __launch_bounds__(512, 2) void conv_wgrad_pair256_kernel(const ng::ConvParams cp, const ng::WgradParams wp, const int conv_wgs,
                                                                      const int conv_tiles, const int wgrad_units) {
-    __shared__ __attribute__((aligned(16))) char lds[S * ng::T256_HALF];
+    __shared__ __attribute__((aligned(16))) char lds[ng::T256_LDS];
     bool again = false;
     if (int(blockIdx.x) < conv_wgs) {
         for (int t = ng_xcd_remap(blockIdx.x, conv_wgs); t < conv_tiles; t += conv_wgs) {
             if (again) ng::t256_bar();
-            ng::conv_tile256<false>(cp, t, lds);
+            ng::conv_tile256(cp, t, lds);
             again = true;
         }
     } else {
         const int y = int(gridDim.x) - conv_wgs;
         for (int u = ng_xcd_remap(int(blockIdx.x) - conv_wgs, y); u < wgrad_units; u += y) {
             if (again) ng::t256_bar();
-            ng::wgrad_tile256<S>(wp, u, lds);
+            ng::wgrad_tile256(wp, u, lds);
             again = true;
         }
     }
@@ -321,46 +317,77 @@ static int pair256_split(const int G, const int conv_tiles, const int conv_nk, c
     return best;
 }
 
+// Which kernel a weight-gradient launch runs on (one place: the launcher and the name query read it); precision 3 off the split tile is
+// demoted to exact fp32 in p.  units: the persistent walks' work items; grid: the launch's workgroups.
+enum WgradKernel { WGRAD_X3_TN256, WGRAD_X3_TN128, WGRAD_TILE256, WGRAD_PERSIST, WGRAD_TILE16, WGRAD_TILE_TN128, WGRAD_TILE_TN64 };
+static const char* const WGRAD_KERNEL_NAMES[] = {"wgrad_x3_kernel<256>", "wgrad_x3_kernel<128>", "wgrad_igemm256_kernel", "wgrad_persist_kernel",
+                                                 "wgrad_igemm16_kernel", "wgrad_igemm_kernel<128>", "wgrad_igemm_kernel<64>"};
+struct WgradRoute { WgradKernel k; int units, grid; };
+static WgradRoute wgrad_route(ng::WgradParams& p, const int algo) {
+    const int G = ng_cu_count();
+    if (p.prec == 3) {
+        if (ng::wgrad_x3_ok(p)) {
+            const int tn = ng::wgrad_x3_tn(p);
+            const int units = (p.N / tn) * ((p.K + 127) >> 7) * p.nsplit * p.nplanes;
+            return {tn == 256 ? WGRAD_X3_TN256 : WGRAD_X3_TN128, units, units < G ? units : G};
+        }
+        p.prec = 0;             // what the split tile does not cover runs as exact fp32
+    }
+    if (algo == 0 && ng::wgrad_tile256_ok(p)) {
+        const int units = (p.N >> 8) * (p.K >> 8) * p.nsplit;
+        return {WGRAD_TILE256, units, units < G ? units : G};
+    }
+    const int tiles = p.ntiles_n * p.ntiles_k * p.nsplit * p.nplanes;
+    // matrix-form problems (the transform-domain weight gradient of a Winograd layer launched on its own) with more units than resident
+    // workgroups: persistent workgroups with the epilogue folded into the next unit's K loop (igemm_tiles.h::wgrad_persist)
+    if (ng::wgrad_persist_ok(p) && ng::wgrad_matrix_form(p) && tiles > 512 && algo != NIRGAN_WGRAD_ONE_UNIT) return {WGRAD_PERSIST, tiles, 512};
+    if (p.pq_bf16) return {WGRAD_TILE16, tiles, tiles};
+    return {p.N > 64 ? WGRAD_TILE_TN128 : WGRAD_TILE_TN64, tiles, tiles};
+}
+
 extern "C" int nirgan_wgrad_igemm(const nirgan_wgrad_desc* d, void* stream) {
     ng::WgradParams p;
     const int rc = ng::build_wgrad_params(d, p);
     if (rc != NIRGAN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p.prec == 3) {
-        if (ng::wgrad_x3_ok(p)) {
-            const int tn = ng::wgrad_x3_tn(p);
-            const int units = (p.N / tn) * ((p.K + 127) >> 7) * p.nsplit * p.nplanes, G = ng_cu_count();
-            if (tn == 256) hipLaunchKernelGGL(wgrad_x3_kernel<256>, dim3(units < G ? units : G), dim3(512), 0, st, p, units);
-            else hipLaunchKernelGGL(wgrad_x3_kernel<128>, dim3(units < G ? units : G), dim3(512), 0, st, p, units);
-            return nirgan_check_launch("wgrad_igemm (three-term split tile)");
-        }
-        p.prec = 0;             // what the split tile does not cover runs as exact fp32
+    const WgradRoute r = wgrad_route(p, d->algo);
+    const dim3 grid(r.grid);
+    switch (r.k) {
+        case WGRAD_X3_TN256: hipLaunchKernelGGL(wgrad_x3_kernel<256>, grid, dim3(512), 0, st, p, r.units); return nirgan_check_launch("wgrad_igemm (three-term split tile)");
+        case WGRAD_X3_TN128: hipLaunchKernelGGL(wgrad_x3_kernel<128>, grid, dim3(512), 0, st, p, r.units); return nirgan_check_launch("wgrad_igemm (three-term split tile)");
+        case WGRAD_TILE256: hipLaunchKernelGGL(wgrad_igemm256_kernel, grid, dim3(512), 0, st, p, r.units); return nirgan_check_launch("wgrad_igemm (256 x 256 tile)");
+        case WGRAD_PERSIST: hipLaunchKernelGGL(wgrad_persist_kernel, grid, dim3(256), 0, st, p); break;
+        case WGRAD_TILE16: hipLaunchKernelGGL(wgrad_igemm16_kernel, grid, dim3(256), 0, st, p); break;
+        case WGRAD_TILE_TN128:
+            if (p.prec == 0) hipLaunchKernelGGL((wgrad_igemm_kernel<128, 0>), grid, dim3(256), 0, st, p);
+            else if (p.prec == 1) hipLaunchKernelGGL((wgrad_igemm_kernel<128, 1>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((wgrad_igemm_kernel<128, 2>), grid, dim3(256), 0, st, p);
+            break;
+        case WGRAD_TILE_TN64:
+            if (p.prec == 0) hipLaunchKernelGGL((wgrad_igemm_kernel<64, 0>), grid, dim3(256), 0, st, p);
+            else if (p.prec == 1) hipLaunchKernelGGL((wgrad_igemm_kernel<64, 1>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((wgrad_igemm_kernel<64, 2>), grid, dim3(256), 0, st, p);
+            break;
     }
-    if (d->algo != NIRGAN_WGRAD_TILE128 && d->algo != NIRGAN_WGRAD_ONE_UNIT && ng::wgrad_tile256_ok(p)) {
-        const int units = (p.N >> 8) * (p.K >> 8) * p.nsplit, G = ng_cu_count();
-        if (d->algo == NIRGAN_WGRAD_RING10) hipLaunchKernelGGL(wgrad_igemm256_kernel<10>, dim3(units < G ? units : G), dim3(512), 0, st, p, units);
-        else hipLaunchKernelGGL(wgrad_igemm256_kernel<8>, dim3(units < G ? units : G), dim3(512), 0, st, p, units);
-        return nirgan_check_launch("wgrad_igemm (256 x 256 tile)");
-    }
-    const dim3 grid(p.ntiles_n * p.ntiles_k * p.nsplit * p.nplanes);
-    // matrix-form problems (the transform-domain weight gradient of a Winograd layer launched on its own) with more units than resident
-    // workgroups: persistent workgroups with the epilogue folded into the next unit's K loop (igemm_tiles.h::wgrad_persist)
-    if (ng::wgrad_persist_ok(p) && ng::wgrad_matrix_form(p) && grid.x > 512 && d->algo != NIRGAN_WGRAD_ONE_UNIT) {
-        hipLaunchKernelGGL(wgrad_persist_kernel, dim3(512), dim3(256), 0, st, p);
-        return nirgan_check_launch("wgrad_igemm");
-    }
-    if (p.pq_bf16) {
-        hipLaunchKernelGGL(wgrad_igemm16_kernel, grid, dim3(256), 0, st, p);
-        return nirgan_check_launch("wgrad_igemm");
-    }
-#define NG_LAUNCH_WGRAD(TN, PREC) hipLaunchKernelGGL((wgrad_igemm_kernel<TN, PREC>), grid, dim3(256), 0, st, p)
-    if (d->N > 64) {
-        if (p.prec == 0) NG_LAUNCH_WGRAD(128, 0); else if (p.prec == 1) NG_LAUNCH_WGRAD(128, 1); else NG_LAUNCH_WGRAD(128, 2);
-    } else {
-        if (p.prec == 0) NG_LAUNCH_WGRAD(64, 0); else if (p.prec == 1) NG_LAUNCH_WGRAD(64, 1); else NG_LAUNCH_WGRAD(64, 2);
-    }
-#undef NG_LAUNCH_WGRAD
     return nirgan_check_launch("wgrad_igemm");
+}
+
+extern "C" const char* nirgan_wgrad_kernel_name(const nirgan_wgrad_desc* d) {
+    ng::WgradParams p;
+    if (ng::build_wgrad_params(d, p) != NIRGAN_OK) return nullptr;
+    return WGRAD_KERNEL_NAMES[wgrad_route(p, d->algo).k];
+}
+
+// Which kernel the fused data-gradient + weight-gradient launch runs on: two ordinary launches for narrow, split-K, mixed-storage or
+// three-term problems; the 256-wide pair for the bf16 operand mode where both halves take that tile (the fused launch divides the CUs
+// between the two kinds of item: it needs at least two; a one-CU device takes the 128-row pair)
+enum PairKernel { PAIR_TWO_LAUNCHES, PAIR_TILE256, PAIR_TILE128 };
+static const char* const PAIR_KERNEL_NAMES[] = {"(two launches)", "conv_wgrad_pair256_kernel", "conv_wgrad_pair_kernel"};
+static PairKernel pair_route(const ng::ConvParams& cp, const ng::WgradParams& wp, const int w_algo) {
+    if (cp.N <= 64 || wp.N <= 64 || cp.ksplit > 1 || (wp.pq_bf16 && !cp.in_bf16) || cp.prec == 3 || wp.prec == 3) return PAIR_TWO_LAUNCHES;
+    if (cp.prec == 1 && cp.algo != NIRGAN_CONV_TILE128 && w_algo != NIRGAN_WGRAD_TILE128 && ng_cu_count() >= 2 && ng::conv_tile256_ok(cp, true, ng_cu_count())
+        && ng::wgrad_tile256_ok(wp)) return PAIR_TILE256;
+    return PAIR_TILE128;
 }
 
 extern "C" int nirgan_conv_wgrad_pair(const nirgan_conv_desc* c, const nirgan_wgrad_desc* w, void* stream) {
@@ -370,52 +397,36 @@ extern "C" int nirgan_conv_wgrad_pair(const nirgan_conv_desc* c, const nirgan_wg
     if (rc != NIRGAN_OK) return rc;
     rc = ng::build_wgrad_params(w, wp);
     if (rc != NIRGAN_OK) return rc;
-    if (c->N <= 64 || w->N <= 64 || c->ksplit > 1 || (wp.pq_bf16 && !cp.in_bf16) || cp.prec == 3 || wp.prec == 3) {      // narrow, split-K, mixed-storage or three-term variants: two ordinary launches
+    const PairKernel k = pair_route(cp, wp, w->algo);
+    if (k == PAIR_TWO_LAUNCHES) {
         rc = nirgan_conv_igemm(c, stream);
         return rc != NIRGAN_OK ? rc : nirgan_wgrad_igemm(w, stream);
     }
     NG_REQUIRE(cp.prec == wp.prec, "conv_wgrad_pair: both halves must use the same precision");
-    // (the fused 256-wide launch divides the CUs between the two kinds of item: it needs at least two; a one-CU device takes the 128-row pair)
-    if (cp.prec == 1 && cp.algo != NIRGAN_CONV_TILE128 && w->algo != NIRGAN_WGRAD_TILE128 && ng_cu_count() >= 2 && ng::conv_tile256_ok(cp, true, ng_cu_count()) && ng::wgrad_tile256_ok(wp)) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (k == PAIR_TILE256) {
         const int conv_tiles = ((cp.M + 255) >> 8) * (cp.N >> 8), units = (wp.N >> 8) * (wp.K >> 8) * wp.nsplit, G = ng_cu_count();
         const int conv_wgs = pair256_split(G, conv_tiles, cp.ntaps * (cp.run >> 6), units, wp.rows_per_split >> 6);
-        if (w->algo == NIRGAN_WGRAD_RING10) hipLaunchKernelGGL(conv_wgrad_pair256_kernel<10>, dim3(G), dim3(512), 0, static_cast<hipStream_t>(stream), cp, wp, conv_wgs, conv_tiles, units);
-        else hipLaunchKernelGGL(conv_wgrad_pair256_kernel<8>, dim3(G), dim3(512), 0, static_cast<hipStream_t>(stream), cp, wp, conv_wgs, conv_tiles, units);
+        hipLaunchKernelGGL(conv_wgrad_pair256_kernel, dim3(G), dim3(512), 0, st, cp, wp, conv_wgs, conv_tiles, units);
         return nirgan_check_launch("conv_wgrad_pair (256 x 256 tiles)");
     }
     const int conv_blocks = cp.mtiles * cp.ntiles;
     const int wgrad_blocks = wp.ntiles_n * wp.ntiles_k * wp.nsplit;
     const dim3 grid(conv_blocks + wgrad_blocks);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (cp.prec == 0) hipLaunchKernelGGL(conv_wgrad_pair_kernel<0>, grid, dim3(256), 0, st, cp, wp, conv_blocks);
-    else if (cp.prec == 1 && cp.in_bf16 && wp.pq_bf16) hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, true, true, true>), grid, dim3(256), 0, st, cp, wp, conv_blocks);
-    else if (cp.prec == 1 && cp.in_bf16) hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, true, true>), grid, dim3(256), 0, st, cp, wp, conv_blocks);
-    else if (cp.prec == 1 && cp.w_bf16) hipLaunchKernelGGL((conv_wgrad_pair_kernel<1, true>), grid, dim3(256), 0, st, cp, wp, conv_blocks);
-    else if (cp.prec == 1) hipLaunchKernelGGL(conv_wgrad_pair_kernel<1>, grid, dim3(256), 0, st, cp, wp, conv_blocks);
-    else hipLaunchKernelGGL(conv_wgrad_pair_kernel<2>, grid, dim3(256), 0, st, cp, wp, conv_blocks);
+    ng::conv_tile_form(cp, [&](auto form) {
+        using F = decltype(form);
+        // (the weight-gradient half reads bf16 twins only next to bf16 activations: pair_route sends the other mix to two launches)
+        if (F::ab16 && wp.pq_bf16) hipLaunchKernelGGL((conv_wgrad_pair_kernel<F::prec, F::wb16, F::ab16, F::ab16>), grid, dim3(256), 0, st, cp, wp, conv_blocks);
+        else hipLaunchKernelGGL((conv_wgrad_pair_kernel<F::prec, F::wb16, F::ab16>), grid, dim3(256), 0, st, cp, wp, conv_blocks);
+    });
     return nirgan_check_launch("conv_wgrad_pair");
-}
-
-extern "C" const char* nirgan_wgrad_kernel_name(const nirgan_wgrad_desc* d) {
-    ng::WgradParams p;
-    if (ng::build_wgrad_params(d, p) != NIRGAN_OK) return nullptr;
-    if (p.prec == 3) {
-        if (ng::wgrad_x3_ok(p)) return ng::wgrad_x3_tn(p) == 256 ? "wgrad_x3_kernel<256>" : "wgrad_x3_kernel<128>";
-        p.prec = 0;
-    }
-    if (d->algo != NIRGAN_WGRAD_TILE128 && d->algo != NIRGAN_WGRAD_ONE_UNIT && ng::wgrad_tile256_ok(p)) return "wgrad_igemm256_kernel";      // (the launcher's own predicate)
-    if (ng::wgrad_persist_ok(p) && ng::wgrad_matrix_form(p) && p.ntiles_n * p.ntiles_k * p.nsplit * p.nplanes > 512 && d->algo != NIRGAN_WGRAD_ONE_UNIT) return "wgrad_persist_kernel";
-    if (p.pq_bf16) return "wgrad_igemm16_kernel";
-    return d->N > 64 ? "wgrad_igemm_kernel<128>" : "wgrad_igemm_kernel<64>";
 }
 
 extern "C" const char* nirgan_conv_wgrad_pair_kernel_name(const nirgan_conv_desc* c, const nirgan_wgrad_desc* w) {
     ng::ConvParams cp;
     ng::WgradParams wp;
     if (ng::build_conv_params(c, cp) != NIRGAN_OK || ng::build_wgrad_params(w, wp) != NIRGAN_OK) return nullptr;
-    if (c->N <= 64 || w->N <= 64 || c->ksplit > 1 || (wp.pq_bf16 && !cp.in_bf16) || cp.prec == 3 || wp.prec == 3) return "(two launches)";
-    if (cp.prec == 1 && cp.algo != NIRGAN_CONV_TILE128 && w->algo != NIRGAN_WGRAD_TILE128 && ng_cu_count() >= 2 && ng::conv_tile256_ok(cp, true, ng_cu_count()) && ng::wgrad_tile256_ok(wp)) return "conv_wgrad_pair256_kernel";
-    return "conv_wgrad_pair_kernel";
+    return PAIR_KERNEL_NAMES[pair_route(cp, wp, w->algo)];
 }
 
 extern "C" int nirgan_reduce_rows(const float* slabs, int nsplit, int N, int K, const int32_t* map,

@@ -215,12 +215,6 @@ __device__ __forceinline__ void conv_x3_persist(const NG_CONST X3Work* const wp,
     };
     auto commitA = [&](char* sA, const int j) {
         bf16x8 H, M, Lo;
-#ifdef NG_X3_DIAG              // diagnostic build only: 0x400 = no conversion (raw bits stored), 0x800 = no LDS stores of the converted rows
-        if (L.p->algo & 0x800) return;
-        if (L.p->algo & 0x400) {
-            H = __builtin_bit_cast(bf16x8, ra[2 * j]); M = __builtin_bit_cast(bf16x8, ra[2 * j + 1]); Lo = H;
-        } else
-#endif
         x3_split8(ra[2 * j], ra[2 * j + 1], H, M, Lo);
         *reinterpret_cast<bf16x8*>(sA + a_wr[j]) = H;
         *reinterpret_cast<bf16x8*>(sA + X3_A_TERM + a_wr[j]) = M;
@@ -318,9 +312,6 @@ __device__ __forceinline__ void conv_x3_persist(const NG_CONST X3Work* const wp,
         __syncthreads();
         const unsigned aad = cur == 0 ? a_ad0 : a_ad1, bad = cur == 0 ? b_ad0 : b_ad1;
         if (more) {
-#ifdef NG_X3_DIAG              // 0x1000 = no fetch of the next K-tile (the loop runs on stale LDS images); 0x800 changes the store count: drain
-            if (L.p->algo & 0x1800) { compute(aad, bad, std::false_type{}, [&]() { if (!(L.p->algo & 0x1000)) { issueB(nB); loadA(); } advance(); }, [&](const int j) { commitA(nA, j); }); return; }
-#endif
             compute(aad, bad, std::true_type{}, [&]() { issueB(nB); loadA(); advance(); }, [&](const int j) { commitA(nA, j); });
         } else {
             compute(aad, bad, std::false_type{}, []() {}, [](const int) {});
@@ -332,9 +323,6 @@ __device__ __forceinline__ void conv_x3_persist(const NG_CONST X3Work* const wp,
     // floats, and leave as whole row segments, 16 bytes per lane.
     auto epilogue = [&]() -> bool {
         const NG_CONST ConvParams& p = *E.p;
-#ifdef NG_X3_DIAG              // diagnostic build only (scripts/diag/x3_parts.sh): what do the epilogue / its stores cost a plane GEMM?
-        if (p.algo & 0x200) return E.m0 + 256 <= p.M;
-#endif
         // (copies: the stores below make the compiler read every field again through `p`)
         const int pM = p.M, pN = p.N, OHW = p.OHW, OW = p.OW, OH = p.OHW / p.OW, out_img = p.out_img, out_row = p.out_row * p.out_stride,
                   out_px = p.out_cs * p.out_stride, out_org = p.out_org, f_img = p.f_img, f_row = p.f_row * p.out_stride, f_px = p.ch * p.out_stride,
@@ -433,9 +421,6 @@ __device__ __forceinline__ void conv_x3_persist(const NG_CONST X3Work* const wp,
                     if (ok[pass]) {
                         f32x4 v = *reinterpret_cast<const f32x4*>(stg + (pass * RPP + lrow) * CW + ((chunk * 4) ^ ((((pass * RPP + lrow) >> 2) & SWM) << 4)));
                         v += bv;
-#ifdef NG_X3_DIAG
-                        if (!(p.algo & 0x100))
-#endif
 #ifdef NG_X3_NT_STORES         // (A/B switch, scripts/diag/ab_build.sh: non-temporal stores -- the consumer's reads then miss: -0.84 % on the step)
                         __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(E.out + ooff[pass]));
 #else
@@ -533,6 +518,10 @@ __device__ __forceinline__ void conv_x3_persist(const NG_CONST X3Work* const wp,
 int ng_launch_conv_x3(const ConvParams* ps, int n, int bn, int nplanes, long long in_plane, long long w3_pstride, long long out_plane,
                       hipStream_t st, const char* what);
 int ng_cu_count_conv();
+// which kernel that launch runs (defined in igemm_conv.hip; the launch and the name queries read it): the four-wave register-fed tile
+// of igemm_x3r.h where every problem takes it (X3R_* = its epilogue form, the KIND template argument), else the eight-wave tile of width bn
+enum X3Kernel { X3R_PLAIN, X3R_STATS, X3R_GENERIC, X3_N128, X3_N64 };
+X3Kernel conv_x3_route(const ConvParams* ps, int n, int bn);
 
 // whether the split tile covers a problem (host): precision 3 with the weight planes present, 32-channel slices, whole 64-column tiles,
 // fp32 tensors on both sides, 32-bit offsets, no split-K
@@ -542,12 +531,13 @@ inline bool conv_x3_ok(const ConvParams& p) {
     if (((p.out_cs | p.out_org | p.out_row | p.out_img) & 3) != 0) return false;
     return (long long)p.N * p.K * 2 < (1ll << 32);
 }
-// 128-column tiles unless N has no such tiles, the caller pins the 64-column tile (NIRGAN_CONV_X3_BN64: A/B), or the problem has fewer
-// 256 x 128 tiles than three quarters of the CUs (one workgroup per CU: twice as many 64-column tiles fill the chip)
+// 128-column tiles unless N has no such tiles or the launch's 1..4 problems have fewer 256 x 128 tiles than three quarters of the CUs
+// (one workgroup per CU: twice as many 64-column tiles fill the chip; the problems of one launch share the chip)
 inline int conv_x3_tiles(const ConvParams& p, const int bn) { return ((p.M + 255) >> 8) * (p.N / bn); }
-inline int conv_x3_bn(const ConvParams& p, const int cus = 256) {
-    if (p.N % 128 != 0 || p.algo == NIRGAN_CONV_X3_BN64) return 64;
-    const long long tiles = (long long)((p.M + 255) >> 8) * (p.N / 128);
+inline int conv_x3_bn(const ConvParams* ps, const int n, const int cus) {
+    if (ps[0].N % 128 != 0) return 64;
+    long long tiles = 0;
+    for (int i = 0; i < n; ++i) tiles += conv_x3_tiles(ps[i], 128);
     return tiles * 4 >= 3ll * cus ? 128 : 64;
 }
 

@@ -20,7 +20,6 @@
 //   G   = [[1/2,0,0],[1/6,1/6,1/6],[1/6,-1/6,1/6],[1/30,1/15,2/15],[16/15,-8/15,4/15],[0,0,1/2]]
 //   A^T = [[1,1,1,1,1,0],[0,1,-1,2,-1/2,0],[0,1,1,4,1/4,0],[0,1,-1,8,-1/8,1]]
 #include "igemm_tiles.h"
-#include "igemm_tile256.h"
 #include "igemm_x3.h"
 #include "instnorm_dev.h"
 #include <stdlib.h>
@@ -541,19 +540,6 @@ __global__ __launch_bounds__(256, 2) void wino6_gemm_kernel(const W6Gemm g) {
                           g.p.out + size_t(plane) * g.out_plane);
 }
 
-// (round 4, A/B: NIRGAN_W6_TILE256) the plane GEMMs on the exact-fp32 form of the 256 x 256 eight-phase tile (igemm_tile256.h), persistent
-// workgroups, one per CU, walking (plane, tile) pairs: measured against wino6_gemm32p_kernel in profiles/r04_plane_gemm_tile256.txt
-__global__ __launch_bounds__(512, 2) void wino6_gemm256_kernel(const W6Gemm g, const int per_plane, const int total) {
-    __shared__ __attribute__((aligned(16))) char lds[ng::T256_LDS];
-    bool again = false;
-    for (int rid = ng_xcd_remap(blockIdx.x, gridDim.x); rid < total; rid += gridDim.x) {
-        if (again) ng::t256_bar();
-        const int plane = rid / per_plane, local = rid - plane * per_plane;
-        ng::conv_tile256<true>(g.p, local, lds, g.p.in + size_t(plane) * g.in_plane, g.p.w + size_t(plane) * g.w_plane, g.p.out + size_t(plane) * g.out_plane);
-        again = true;
-    }
-}
-
 // The data gradient's plane GEMMs and the 36 weight-gradient problems of the same layer in ONE grid (both read what the dY pass just
 // wrote): the long weight-gradient blocks (18 K-steps) are dispatched first, the GEMM blocks (8 K-steps) pack behind them, so neither
 // launch pays its own partly filled last round.  32-k stages for both halves (the direct tile and the weight-gradient tile share 64 KB).
@@ -901,11 +887,6 @@ __device__ __forceinline__ void w6_gemmp_body(const W6G16& p, const int first, c
             break;
         }
     }
-}
-
-__global__ __launch_bounds__(256, 2) void wino6_gemm16p_kernel(const W6G16 p) {
-    __shared__ __attribute__((aligned(16))) char lds[w6p_lds<16>()];
-    w6_gemmp_body<16>(p, blockIdx.x, gridDim.x, lds);
 }
 
 __global__ __launch_bounds__(256, 2) void wino6_gemm32p_kernel(const W6G16 p) {
@@ -1288,6 +1269,11 @@ __device__ __forceinline__ void wino6_wgrad_finish_body(const W6Fin& p) {
 // the descriptors' `r` field selects the variant: 0 / 3 = F(4x4,3x3), 4 = F(4x4,4x4), 6 = F(6x6,3x3)
 static inline int w6_r(int r) { return r == 0 ? 3 : r; }
 static inline bool w6_known(int v) { return v == 3 || v == 4 || v == 6; }
+// the nirgan_wino6_desc.algo values (the plane GEMMs and the transforms read the same field)
+static inline bool w6_algo_known(int a) {
+    return a == 0 || a == NIRGAN_W6_ONE_TILE || a == NIRGAN_W6_DIRECT_TILE || a == NIRGAN_W6_X3_R4 || a == NIRGAN_W6_PATCH_PER_THREAD || a == NIRGAN_W6_PATCH_PER_LANES;
+}
+#define W6_ALGOS "0, NIRGAN_W6_ONE_TILE, _DIRECT_TILE, _X3_R4, _PATCH_PER_THREAD or _PATCH_PER_LANES"
 static inline int w6_filter(int v) { return v == 6 ? 3 : v; }            // filter size
 static inline int w6_mo(int v) { return v == 6 ? 6 : 4; }                // outputs per tile and dimension
 static inline int w6_np(int v) { const int n = w6_mo(v) + w6_filter(v) - 1; return n * n; }      // planes: 36 / 49 / 64
@@ -1339,6 +1325,7 @@ static int w6_input_impl(const nirgan_wino6_desc* d, const nirgan_wino_dy_desc* 
     NG_REQUIRE(d && d->V && (d->x || ny || nb), "wino6_input: null pointer");
     const int v = w6_r(d->r), np = w6_np(v), r = w6_filter(v), mo = w6_mo(v);
     NG_REQUIRE(w6_known(v), "wino6_input: variant %d (3, 4 or 6)", v);
+    NG_REQUIRE(w6_algo_known(d->algo), "wino6_input: algo=%d (" W6_ALGOS ")", d->algo);
     NG_REQUIRE(r == 3 || (!ny && !nb), "wino6_input: the fused variants exist for the 3x3 filter");
     NG_REQUIRE(!nb || (v == 6 && d->C % 32 == 0), "wino6_input_dy_norm: F(6x6,3x3) with C %% 32 == 0 only");
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->C > 0 && d->C % 4 == 0, "wino6_input: bad shape B=%d H=%d W=%d C=%d", d->B, d->H, d->W, d->C);
@@ -1440,6 +1427,7 @@ static int w6_gemm_params(const nirgan_wino6_desc* d, W6Gemm& g, long long& T) {
     NG_REQUIRE(d && (d->U || d->U3) && d->V && d->M && d->zero_page, "wino6_gemm: null pointer");
     const int v = w6_r(d->r), np = w6_np(v);
     NG_REQUIRE(w6_known(v), "wino6_gemm: variant %d (3, 4 or 6)", v);
+    NG_REQUIRE(w6_algo_known(d->algo), "wino6_gemm: algo=%d (" W6_ALGOS ")", d->algo);
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->C > 0 && d->C % 4 == 0 && d->K > 64 && d->K % 4 == 0, "wino6_gemm: C %% 4 == 0, K > 64, K %% 4 == 0 (C=%d K=%d)", d->C, d->K);
     T = w6_tiles(d->B, d->H, d->W, v);
     NG_REQUIRE(T * d->C < (1ll << 31) && T * d->K < (1ll << 31), "wino6_gemm: problem too large for 32-bit offsets");
@@ -1459,7 +1447,7 @@ static int w6_gemm_params(const nirgan_wino6_desc* d, W6Gemm& g, long long& T) {
     return NIRGAN_OK;
 }
 
-// The persistent tile (wino6_gemm16p_kernel) where it measures faster: C = 256 (16 K-steps per tile: 186 -> 165 us at T = 4096, 211 ->
+// The persistent tile (wino6_gemm32p_kernel; first measured on 16-k stages) where it measures faster: C = 256 (16 K-steps per tile: 186 -> 165 us at T = 4096, 211 ->
 // 196 at T = 4624, 251 -> 236 for the PatchGAN's 49 x [2048 x 256] x [512]).  At C = 512 a tile is twice as long and the uneven last
 // round of fixed assignments costs more than the folded epilogue saves (579 vs 536 us for the PatchGAN layer's pair launch).
 // (C = 512, the PatchGAN's F(4x4,4x4) data gradient: the plain GEMM gains 12 % as persistent workgroups, the pair launch loses 9 %)
@@ -1479,51 +1467,60 @@ static W6G16 w6_g16_params(const nirgan_wino6_desc* d, long long T) {
     return q;
 }
 
-// which kernel a descriptor's plane GEMMs run on (one place: the launchers and the name queries read it)
-enum W6Choice { W6_PERSIST32, W6_PERSIST16K, W6_ONE_TILE16, W6_DIRECT };
-static W6Choice w6_gemm_choice(const nirgan_wino6_desc* d, bool pair) {
-    if (d->C % 16 != 0 || d->algo == NIRGAN_W6_DIRECT_TILE) return W6_DIRECT;
-    if (pair) {                                        // the pair launch has the persistent 32-k form and the direct-tile form
-        return (w6_persistent_ok(d, true) && d->algo != NIRGAN_W6_ONE_TILE) ? W6_PERSIST32 : W6_DIRECT;
-    }
-    if (w6_persistent_ok(d, false) && d->algo != NIRGAN_W6_ONE_TILE) return d->algo == NIRGAN_W6_PERSIST16 ? W6_PERSIST16K : W6_PERSIST32;
-    return W6_ONE_TILE16;
+// precision 3 for the plane GEMMs: the three bf16 planes of U are there and the split tile's shapes apply; g.p then describes the
+// split tile's launch (nirgan_wino6_desc.algo = NIRGAN_W6_X3_R4 asks for the four-wave register-fed tile where it applies)
+static bool w6_x3(const nirgan_wino6_desc* d, W6Gemm& g) {
+    if (!(d->U3 != nullptr && d->C % 32 == 0 && d->K % 64 == 0 && g.p.off32 && (long long)w6_np(w6_r(d->r)) * d->K * d->C * 2 < (1ll << 40))) return false;
+    g.p.prec = 3;
+    g.p.w3 = static_cast<const unsigned short*>(d->U3);
+    g.p.w3_plane = (long long)w6_np(w6_r(d->r)) * d->K * d->C;
+    g.p.algo = d->algo == NIRGAN_W6_X3_R4 ? NIRGAN_CONV_X3_R4 : 0;
+    return true;
 }
 
-// precision 3 for the plane GEMMs: the three bf16 planes of U are there and the split tile's shapes apply
-static bool w6_x3(const nirgan_wino6_desc* d, const W6Gemm& g) {
-    return d->U3 != nullptr && d->C % 32 == 0 && d->K % 64 == 0 && g.p.off32 && (long long)w6_np(w6_r(d->r)) * d->K * d->C * 2 < (1ll << 40);
-}
-static bool w6_x3_desc(const nirgan_wino6_desc* d) {
-    W6Gemm g;
-    long long T;
-    return d && d->U3 != nullptr && w6_gemm_params(d, g, T) == NIRGAN_OK && w6_x3(d, g);
+// Which kernel a descriptor's plane GEMMs run on (one place: the launchers and the name queries read it).  pair: the fused launch with
+// the weight gradient, which has the persistent 32-k form and the direct-tile form (the split tile runs the pair as two launches).
+enum W6Choice { W6_SPLIT3, W6_PERSIST32, W6_ONE_TILE16, W6_DIRECT };
+struct W6Route { W6Choice k; ng::X3Kernel x3; int bn; };       // W6_SPLIT3: the split tile's kernel and width (ng_launch_conv_x3)
+static W6Route w6_gemm_route(const nirgan_wino6_desc* d, W6Gemm& g, const bool pair) {
+    if (w6_x3(d, g)) {
+        const int bn = d->K % 128 == 0 ? 128 : 64;
+        return {W6_SPLIT3, ng::conv_x3_route(&g.p, 1, bn), bn};
+    }
+    if (d->C % 16 != 0 || d->algo == NIRGAN_W6_DIRECT_TILE) return {W6_DIRECT};
+    if (w6_persistent_ok(d, pair) && d->algo != NIRGAN_W6_ONE_TILE) return {W6_PERSIST32};
+    return {pair ? W6_DIRECT : W6_ONE_TILE16};
 }
 
 extern "C" const char* nirgan_wino6_gemm_kernel_name(const nirgan_wino6_desc* d) {
-    if (!d) return "";
-    if (w6_x3_desc(d)) return d->K % 128 == 0 ? (d->algo == NIRGAN_W6_X3_R4 ? "conv_x3r_kernel<128> (planes)" : "conv_x3_kernel<128> (planes)") : "conv_x3_kernel<64> (planes)";
-    if (d->algo == NIRGAN_W6_TILE256 && d->C % 32 == 0 && d->K % 256 == 0) return "wino6_gemm256_kernel";
-    switch (w6_gemm_choice(d, false)) {
-        case W6_PERSIST32: return "wino6_gemm32p_kernel";
-        case W6_PERSIST16K: return "wino6_gemm16p_kernel";
-        case W6_ONE_TILE16: return "wino6_gemm16_kernel";
-        default: return "wino6_gemm_kernel";
-    }
+    W6Gemm g;
+    long long T;
+    if (!d || w6_gemm_params(d, g, T) != NIRGAN_OK) return "";
+    static const char* const X3_NAMES[] = {"conv_x3r_kernel<128> (planes)", "conv_x3r_kernel<128> (planes)", "conv_x3r_kernel<128> (planes)",
+                                           "conv_x3_kernel<128> (planes)", "conv_x3_kernel<64> (planes)"};       // by ng::X3Kernel
+    static const char* const NAMES[] = {nullptr, "wino6_gemm32p_kernel", "wino6_gemm16_kernel", "wino6_gemm_kernel"};     // by W6Choice
+    const W6Route r = w6_gemm_route(d, g, false);
+    return r.k == W6_SPLIT3 ? X3_NAMES[r.x3] : NAMES[r.k];
 }
 
-// the weight-gradient half of a pair launch walks its units persistently when it has the plane-matrix form
-static bool w6_pair_wgrad_persistent(const ng::WgradParams& wp, const nirgan_wgrad_desc* w) {
-    return ng::wgrad_persist_ok(wp) && ng::wgrad_matrix_form(wp) && w->algo != NIRGAN_WGRAD_ONE_UNIT;
+// The fused launch's kernel: "" = two ordinary launches (narrow or non-fp32 weight gradients, the split tile); the weight-gradient half
+// walks its units persistently next to the persistent GEMM form when it has the plane-matrix form
+enum W6PairKernel { W6P_TWO_LAUNCHES, W6P_PAIR16P, W6P_PAIR16, W6P_PAIR };
+static W6PairKernel w6_pair_route(const nirgan_wino6_desc* d, W6Gemm& g, const ng::WgradParams& wp, const nirgan_wgrad_desc* w) {
+    if (wp.N <= 64 || wp.prec != 0 || wp.pq_bf16) return W6P_TWO_LAUNCHES;
+    const W6Choice k = w6_gemm_route(d, g, true).k;
+    if (k == W6_SPLIT3) return W6P_TWO_LAUNCHES;
+    if (k != W6_PERSIST32) return W6P_PAIR;
+    return ng::wgrad_persist_ok(wp) && ng::wgrad_matrix_form(wp) && w->algo != NIRGAN_WGRAD_ONE_UNIT ? W6P_PAIR16P : W6P_PAIR16;
 }
 
 extern "C" const char* nirgan_wino6_pair_kernel_name(const nirgan_wino6_desc* d, const nirgan_wgrad_desc* w) {
-    if (!d || !w) return "";
+    W6Gemm g;
+    long long T;
     ng::WgradParams wp;
-    if (ng::build_wgrad_params(w, wp) != NIRGAN_OK) return "";
-    if (w->N <= 64 || wp.prec != 0 || wp.pq_bf16 || w6_x3_desc(d)) return "";                      // two ordinary launches
-    if (w6_gemm_choice(d, true) == W6_PERSIST32) return w6_pair_wgrad_persistent(wp, w) ? "wino6_pair16p_kernel" : "wino6_pair16_kernel";
-    return "wino6_pair_kernel";
+    if (!d || !w || w6_gemm_params(d, g, T) != NIRGAN_OK || ng::build_wgrad_params(w, wp) != NIRGAN_OK) return "";
+    static const char* const NAMES[] = {"", "wino6_pair16p_kernel", "wino6_pair16_kernel", "wino6_pair_kernel"};      // by W6PairKernel
+    return NAMES[w6_pair_route(d, g, wp, w)];
 }
 
 extern "C" int nirgan_wino6_gemm_wgrad_pair(const nirgan_wino6_desc* d, const nirgan_wgrad_desc* w, void* stream) {
@@ -1534,25 +1531,24 @@ extern "C" int nirgan_wino6_gemm_wgrad_pair(const nirgan_wino6_desc* d, const ni
     ng::WgradParams wp;
     rc = ng::build_wgrad_params(w, wp);
     if (rc != NIRGAN_OK) return rc;
-    if (w->N <= 64 || wp.prec != 0 || wp.pq_bf16 || w6_x3(d, g)) {           // not the wide fp32 tile, or the three-term split tiles: two ordinary launches
+    const W6PairKernel k = w6_pair_route(d, g, wp, w);
+    if (k == W6P_TWO_LAUNCHES) {
         rc = nirgan_wino6_gemm(d, stream);
         return rc != NIRGAN_OK ? rc : nirgan_wgrad_igemm(w, stream);
     }
     NG_REQUIRE(d->U != nullptr, "wino6_gemm_wgrad_pair: U is required unless the three-term split tile takes the launch");
     const int wgrad_blocks = wp.ntiles_n * wp.ntiles_k * wp.nsplit * wp.nplanes;
-    if (w6_gemm_choice(d, true) == W6_PERSIST32) {
-        NG_REQUIRE(ng_aligned16(d->U) && ng_aligned16(d->V) && ng_aligned16(d->M) && ng_aligned16(d->zero_page), "wino6_gemm_wgrad_pair: pointers must be 16-byte aligned");
-        const W6G16 q = w6_g16_params(d, T);
-        const int gemm_blocks = q.total < 512 ? q.total : 512;
-        // the persistent weight-gradient walk needs the plane-matrix form (one tap, unit stride, one image row) and rows in every split
-        if (w6_pair_wgrad_persistent(wp, w)) {
-            hipLaunchKernelGGL(wino6_pair16p_kernel, dim3(gemm_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), q, gemm_blocks, wp);
-            return nirgan_check_launch("wino6_gemm_wgrad_pair");
-        }
-        hipLaunchKernelGGL(wino6_pair16_kernel, dim3(gemm_blocks + wgrad_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), q, gemm_blocks, wp, wgrad_blocks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (k == W6P_PAIR) {
+        hipLaunchKernelGGL(wino6_pair_kernel, dim3(g.total + wgrad_blocks), dim3(256), 0, st, g, wp, wgrad_blocks, 1);
         return nirgan_check_launch("wino6_gemm_wgrad_pair");
     }
-    hipLaunchKernelGGL(wino6_pair_kernel, dim3(g.total + wgrad_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), g, wp, wgrad_blocks, 1);
+    NG_REQUIRE(ng_aligned16(d->U) && ng_aligned16(d->V) && ng_aligned16(d->M) && ng_aligned16(d->zero_page), "wino6_gemm_wgrad_pair: pointers must be 16-byte aligned");
+    const W6G16 q = w6_g16_params(d, T);
+    const int gemm_blocks = q.total < 512 ? q.total : 512;
+    // the persistent weight-gradient walk needs the plane-matrix form (one tap, unit stride, one image row) and rows in every split
+    if (k == W6P_PAIR16P) hipLaunchKernelGGL(wino6_pair16p_kernel, dim3(gemm_blocks), dim3(256), 0, st, q, gemm_blocks, wp);
+    else hipLaunchKernelGGL(wino6_pair16_kernel, dim3(gemm_blocks + wgrad_blocks), dim3(256), 0, st, q, gemm_blocks, wp, wgrad_blocks);
     return nirgan_check_launch("wino6_gemm_wgrad_pair");
 }
 
@@ -1561,38 +1557,21 @@ extern "C" int nirgan_wino6_gemm(const nirgan_wino6_desc* d, void* stream) {
     long long T;
     const int rc0 = w6_gemm_params(d, g, T);
     if (rc0 != NIRGAN_OK) return rc0;
-    const W6Choice ch = w6_gemm_choice(d, false);
-    if (w6_x3(d, g)) {
-        // precision 3: the plane GEMMs on the bf16 pipe, V split in the kernel, U from its three bf16 planes (nirgan_wino6_weights_x3)
-        g.p.prec = 3;
-        g.p.w3 = static_cast<const unsigned short*>(d->U3);
-        g.p.w3_plane = (long long)w6_np(w6_r(d->r)) * d->K * d->C;
-        g.p.algo = d->algo == NIRGAN_W6_X3_R4 ? NIRGAN_CONV_X3_R4 : 0;       // (A/B: the four-wave register-fed tile)
-#ifdef NG_X3_DIAG
-        g.p.algo = d->algo & 0xf00;          // diagnostic build only: the epilogue switches of igemm_x3.h
-#endif
-        return ng::ng_launch_conv_x3(&g.p, 1, d->K % 128 == 0 ? 128 : 64, w6_np(w6_r(d->r)), g.in_plane, g.w_plane, g.out_plane,
-                                     static_cast<hipStream_t>(stream), "wino6_gemm (three-term split tile)");
-    }
+    const W6Route r = w6_gemm_route(d, g, false);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (r.k == W6_SPLIT3)        // precision 3: the plane GEMMs on the bf16 pipe, V split in the kernel, U from its three bf16 planes (nirgan_wino6_weights_x3)
+        return ng::ng_launch_conv_x3(&g.p, 1, r.bn, w6_np(w6_r(d->r)), g.in_plane, g.w_plane, g.out_plane, st, "wino6_gemm (three-term split tile)");
     NG_REQUIRE(d->U != nullptr, "wino6_gemm: U is required unless the three-term split tile takes the launch (U3, C %% 32 == 0, K %% 64 == 0)");
-    if (d->algo == NIRGAN_W6_TILE256 && d->C % 32 == 0 && d->K % 256 == 0 && g.p.off32) {
-        const int per_plane = ((g.p.M + 255) >> 8) * (g.p.N >> 8), total = w6_np(w6_r(d->r)) * per_plane;
-        const int cus = ng::ng_cu_count_conv();
-        hipLaunchKernelGGL(wino6_gemm256_kernel, dim3(total < cus ? total : cus), dim3(512), 0, static_cast<hipStream_t>(stream), g, per_plane, total);
-        return nirgan_check_launch("wino6_gemm (256-wide tile)");
-    }
-    if (ch == W6_DIRECT) {
-        hipLaunchKernelGGL(wino6_gemm_kernel, dim3(g.total), dim3(256), 0, static_cast<hipStream_t>(stream), g);
+    if (r.k == W6_DIRECT) {
+        hipLaunchKernelGGL(wino6_gemm_kernel, dim3(g.total), dim3(256), 0, st, g);
         return nirgan_check_launch("wino6_gemm");
     }
     NG_REQUIRE(ng_aligned16(d->U) && ng_aligned16(d->V) && ng_aligned16(d->M) && ng_aligned16(d->zero_page), "wino6_gemm: pointers must be 16-byte aligned");
     const W6G16 q = w6_g16_params(d, T);
-    const int grid = q.total < 512 ? q.total : 512;           // persistent workgroups, epilogue folded into the next tile's K loop: 2 per CU
-    // 32-k stages (half the barriers per product; 76 KB of LDS, still two workgroups per CU): 145.8 -> 141.7 us once the loader
-    // carries no vector arithmetic (before that: no difference)
-    if (ch == W6_PERSIST32) hipLaunchKernelGGL(wino6_gemm32p_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), q);
-    else if (ch == W6_PERSIST16K) hipLaunchKernelGGL(wino6_gemm16p_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), q);
-    else hipLaunchKernelGGL(wino6_gemm16_kernel, dim3(q.total), dim3(256), 0, static_cast<hipStream_t>(stream), q);       // 16-k stages, up to four resident workgroups per CU
+    // persistent workgroups, epilogue folded into the next tile's K loop, 2 per CU, on 32-k stages (half the barriers per product; 76 KB of
+    // LDS, still two workgroups per CU): 145.8 -> 141.7 us once the loader carries no vector arithmetic (before that: no difference)
+    if (r.k == W6_PERSIST32) hipLaunchKernelGGL(wino6_gemm32p_kernel, dim3(q.total < 512 ? q.total : 512), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(wino6_gemm16_kernel, dim3(q.total), dim3(256), 0, st, q);       // 16-k stages, up to four resident workgroups per CU
     return nirgan_check_launch("wino6_gemm");
 }
 
@@ -1600,6 +1579,7 @@ extern "C" int nirgan_wino6_output(const nirgan_wino6_desc* d, void* stream) {
     NG_REQUIRE(d && d->M && (d->y || d->fuse_gz), "wino6_output: null pointer");
     const int v = w6_r(d->r), mo = w6_mo(v);
     NG_REQUIRE(w6_known(v), "wino6_output: variant %d (3, 4 or 6)", v);
+    NG_REQUIRE(w6_algo_known(d->algo), "wino6_output: algo=%d (" W6_ALGOS ")", d->algo);
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->K > 0 && d->K % 4 == 0, "wino6_output: bad shape");
     NG_REQUIRE(ng_aligned16(d->M) && ng_aligned16(d->y) && ng_aligned16(d->bias), "wino6_output: pointers must be 16-byte aligned");
     const long long T = w6_tiles(d->B, d->H, d->W, v);

@@ -13,7 +13,7 @@ import os
 
 class Options:
     # plane GEMMs of the Winograd layers: nirgan_wino6_desc.algo (0 = persistent workgroups on 32-k stages where they apply,
-    # lib.W6_ONE_TILE / W6_PERSIST16 / W6_DIRECT_TILE)
+    # lib.W6_ONE_TILE / W6_DIRECT_TILE)
     w6_gemm_algo: int = 0
     # weight-gradient launches of plane-matrix form: nirgan_wgrad_desc.algo (0 = persistent walk, lib.WGRAD_ONE_UNIT)
     wgrad_algo: int = 0

@@ -45,8 +45,7 @@ def conv_problem(B, H, cin, cout, k, s):
     ctx.keep.append(wp)
     tw, plane = split3(wp)
     arms = {}
-    for name, prec, algo in (("fp32 (precision 0)", 0, 0), ("bf16x3 two terms (precision 2)", 2, 0), ("three terms, six products (precision 3)", 3, 0),
-                             ("   ... on 256 x 64 tiles", 3, L.CONV_X3_BN64)):
+    for name, prec, algo in (("fp32 (precision 0)", 0, 0), ("bf16x3 two terms (precision 2)", 2, 0), ("three terms, six products (precision 3)", 3, 0)):
         y = Halo(ctx, B, OH, OH, cout, 0)
         d = emit_conv(None, ctx, x, G.conv_fwd_taps(k, cin), wp, None, y, N=cout, OH=OH, OW=OH, in_stride=s, allow_split=False)
         d.precision = prec

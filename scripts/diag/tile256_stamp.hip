@@ -3,9 +3,6 @@
 // K loop, statistics, epilogue -- and what clock does the chip hold (s_memtime against s_memrealtime).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o scripts/diag/tile256_stamp scripts/diag/tile256_stamp.hip
 #define NG_DIAG256 1
-#ifndef RING
-#define RING 8
-#endif
 #include "../../nir-gan_amd/csrc/igemm_tile256.h"
 #include <vector>
 #include <cstring>
@@ -14,8 +11,8 @@
 void nirgan_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fprintf(stderr, "\n"); }
 
 __global__ __launch_bounds__(512, 2) void k(const ng::ConvParams p) {
-    __shared__ __attribute__((aligned(16))) char lds[RING * ng::T256_HALF];
-    ng::conv_tile256<false, RING>(p, ng_xcd_remap(blockIdx.x, gridDim.x), lds);
+    __shared__ __attribute__((aligned(16))) char lds[ng::T256_LDS];
+    ng::conv_tile256(p, ng_xcd_remap(blockIdx.x, gridDim.x), lds);
 }
 
 static unsigned short bf16_of(float f) { unsigned u; memcpy(&u, &f, 4); return (unsigned short)((u + 0x7FFF + ((u >> 16) & 1)) >> 16); }

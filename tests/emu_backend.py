@@ -94,6 +94,12 @@ def halo_images(h, H, P):
     return out
 
 
+# the descriptors' `algo` values the library accepts (include/nirgan_hip.h); any other fails with NIRGAN_ERR_ARG
+CONV_ALGOS = (0, 1, 4)                  # default, NIRGAN_CONV_TILE128, NIRGAN_CONV_X3_R4
+WGRAD_ALGOS = (0, 1, 2)                 # default, NIRGAN_WGRAD_ONE_UNIT, NIRGAN_WGRAD_TILE128
+W6_ALGOS = (0, 1, 3, 5, 16, 17)         # default, NIRGAN_W6_ONE_TILE, _DIRECT_TILE, _X3_R4, _PATCH_PER_THREAD, _PATCH_PER_LANES
+
+
 def reflect(i, n):
     i = np.abs(i)
     return np.where(i >= n, 2 * (n - 1) - i, i)
@@ -121,6 +127,8 @@ class EmuBackend:
     def nirgan_conv_igemm(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("conv")
+        if d.algo not in CONV_ALGOS:
+            return self._fail(f"conv: algo={d.algo}")
         if d.run % 4 or d.in_cs % 4:
             return self._fail("conv: run/in_cs not multiple of 4")
         K = d.ntaps * d.run
@@ -225,6 +233,8 @@ class EmuBackend:
 
     def nirgan_wgrad_igemm(self, ref, stream=None):
         d = obj(ref)
+        if d.algo not in WGRAD_ALGOS:
+            return self._fail(f"wgrad_igemm: algo={d.algo}")
         if d.nplanes > 1:                      # independent problems of identical geometry: run them one by one
             import copy
             K = d.ntaps * d.run
@@ -286,6 +296,8 @@ class EmuBackend:
         return 0
 
     def nirgan_conv_wgrad_pair(self, cref, wref, stream=None):
+        if obj(wref).algo not in WGRAD_ALGOS:             # (the library checks both descriptors before it launches anything)
+            return self._fail(f"wgrad_igemm: algo={obj(wref).algo}")
         rc = self.nirgan_conv_igemm(cref)
         return rc if rc else self.nirgan_wgrad_igemm(wref)
 
@@ -529,6 +541,8 @@ class EmuBackend:
     def nirgan_wino6_input(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("wino6_in")
+        if d.algo not in W6_ALGOS:
+            return self._fail(f"wino6_input: algo={d.algo}")
         v = self._r6(d.r)
         if v not in self._W6:
             return self._fail("wino6_input: variant")
@@ -546,6 +560,8 @@ class EmuBackend:
     def nirgan_wino6_input_norm(self, ref, y, mean, rstd, act, slope, stream=None):
         d = obj(ref)
         self.calls.append("wino6_in_norm")
+        if d.algo not in W6_ALGOS:
+            return self._fail(f"wino6_input: algo={d.algo}")
         v = self._r6(d.r)
         if v not in (3, 6):
             return self._fail("wino6_input_norm: 3x3 filters only")
@@ -561,6 +577,8 @@ class EmuBackend:
     def nirgan_wino6_gemm(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("wino6_gemm")
+        if d.algo not in W6_ALGOS:
+            return self._fail(f"wino6_gemm: algo={d.algo}")
         T = self.nirgan_wino6_tiles_r(d.B, d.H, d.W, d.r)
         nplanes = self._geo6(self._r6(d.r))[2] ** 2
         if d.K <= 64 or d.K % 4 or d.C % 4 or d.V_elems < nplanes * T * d.C or d.M_elems < nplanes * T * d.K:
@@ -610,12 +628,16 @@ class EmuBackend:
         return b"emulated_wino6_pair"
 
     def nirgan_wino6_gemm_wgrad_pair(self, cref, wref, stream=None):
+        if obj(wref).algo not in WGRAD_ALGOS:
+            return self._fail(f"wgrad_igemm: algo={obj(wref).algo}")
         rc = self.nirgan_wino6_gemm(cref)
         return rc if rc else self.nirgan_wgrad_igemm(wref)
 
     def nirgan_wino6_output(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("wino6_out")
+        if d.algo not in W6_ALGOS:
+            return self._fail(f"wino6_output: algo={d.algo}")
         B, H, W, K = d.B, d.H, d.W, d.K
         v = self._r6(d.r)
         r, mo, n = self._geo6(v)

@@ -256,7 +256,8 @@ def test_pair256_repeated_launches_agree_bitwise():
     assert int(bad.item()) == 0, f"{int(bad.item())} differing results in {150 * SOAK} launches"
 
 
-# ------------------------------------------------------------------ the same tile in exact fp32 (v_mfma_f32_32x32x2_f32)
+# ------------------------------------------------------------------ exact fp32 (v_mfma_f32_32x32x2_f32) stays on the 128-row tile
+# (an fp32 form of the 256-wide tile measured within 1 % of it and was retired: DESIGN_HISTORY.md)
 def _problem_f32(B, H, W, Cin, Cout, k, stride, bias, seed=0):
     ctx = Ctx(DEV, "fp32")
     g = torch.Generator().manual_seed(seed)
@@ -271,15 +272,11 @@ def _problem_f32(B, H, W, Cin, Cout, k, stride, bias, seed=0):
     ctx.keep.append(wp)          # (the descriptors hold its ADDRESS only: without this the caching allocator hands the block to the next clone())
     L.call("nirgan_pack_rows", w.data_ptr(), w.numel(), spec.row_stride, ctx.i32(spec.index_map).data_ptr(), wp.data_ptr(), spec.N, spec.K, None)
     torch.cuda.synchronize()
-    outs, descs = [], []
-    for algo in (L.CONV_TILE256, 0):
-        y = Halo(ctx, B, OH, OW, Cout, 0)
-        y.t.fill_(float("nan"))
-        d = emit_conv(None, ctx, x, G.conv_fwd_taps(k, Cin), wp, b, y, N=Cout, OH=OH, OW=OW, in_stride=stride, allow_split=False)
-        d.algo = algo
-        outs.append(y)
-        descs.append(d)
-    return ctx, x, w, b, outs, descs
+    y = Halo(ctx, B, OH, OW, Cout, 0)
+    y.t.fill_(float("nan"))
+    d = emit_conv(None, ctx, x, G.conv_fwd_taps(k, Cin), wp, b, y, N=Cout, OH=OH, OW=OW, in_stride=stride, allow_split=False)
+    d.algo = 0
+    return ctx, x, w, b, y, d
 
 
 F32_CASES = [
@@ -293,32 +290,28 @@ F32_CASES = [
 
 
 @pytest.mark.parametrize("case", F32_CASES)
-def test_tile256_fp32_against_the_128_row_tile_and_float64(case):
-    """Exact-fp32 mode, NIRGAN_CONV_TILE256 (the default keeps the 128-row tile there): the 256-wide tile against the 128-row tile (fp32 summation order only: both are exact fp32 FMA
-    chains) and against torch's conv2d in float64 (the reference's nn.Conv2d arithmetic, model/networks.py:349,405-427)."""
+def test_fp32_128_row_tile_against_float64(case):
+    """Exact-fp32 mode on the shapes the 256-wide tile was measured on: the default launch is the 128-row tile, every row and column
+    written, within 1e-5 of torch's conv2d in float64 (the reference's nn.Conv2d arithmetic, model/networks.py:349,405-427)."""
     B, H, W, Cin, Cout, k, stride, bias = case
-    ctx, x, w, b, (y256, y128), (d256, d128) = _problem_f32(*case)
-    assert L.backend().nirgan_conv_kernel_name(C.byref(d256)).decode() == "conv_igemm256_kernel<fp32>"
-    assert L.backend().nirgan_conv_kernel_name(C.byref(d128)).decode() == "conv_igemm_kernel<128>"
-    L.call("nirgan_conv_igemm", C.byref(d256), None)
-    L.call("nirgan_conv_igemm", C.byref(d128), None)
+    ctx, x, w, b, y, d = _problem_f32(*case)
+    assert L.backend().nirgan_conv_kernel_name(C.byref(d)).decode() == "conv_igemm_kernel<128>"
+    L.call("nirgan_conv_igemm", C.byref(d), None)
     torch.cuda.synchronize()
-    assert torch.isfinite(y256.t).all(), "rows or columns left unwritten"
-    assert _rel(y256.t, y128.t) <= 1e-5, f"256-wide tile vs 128-row tile: {_rel(y256.t, y128.t):.3e}"
-    if B * H * W <= 70000:
-        ref = torch.nn.functional.conv2d(x.t.double().permute(0, 3, 1, 2), w.double(), None if b is None else b.double(), stride=stride).permute(0, 2, 3, 1)
-        assert _rel(y256.t, ref.float()) <= 1e-5, f"256-wide tile vs float64 conv2d: {_rel(y256.t, ref.float()):.3e}"
+    assert torch.isfinite(y.t).all(), "rows or columns left unwritten"
+    ref = torch.nn.functional.conv2d(x.t.double().permute(0, 3, 1, 2), w.double(), None if b is None else b.double(), stride=stride).permute(0, 2, 3, 1)
+    assert _rel(y.t, ref.float()) <= 1e-5, f"128-row tile vs float64 conv2d: {_rel(y.t, ref.float()):.3e}"
 
 
-def test_tile256_fp32_repeated_launches_agree_bitwise():
+def test_fp32_128_row_tile_repeated_launches_agree_bitwise():
     for case in (F32_CASES[0], F32_CASES[2]):
-        ctx, x, w, b, (y256, _), (d256, _) = _problem_f32(*case, seed=3)
-        L.call("nirgan_conv_igemm", C.byref(d256), None)
+        ctx, x, w, b, y, d = _problem_f32(*case, seed=3)
+        L.call("nirgan_conv_igemm", C.byref(d), None)
         torch.cuda.synchronize()
-        first = y256.t.clone()
+        first = y.t.clone()
         bad = torch.zeros((), dtype=torch.int64, device=DEV)
         for it in range(100 * SOAK):
-            y256.t.fill_(0)
-            L.call("nirgan_conv_igemm", C.byref(d256), None)
-            bad += (y256.t != first).any().to(torch.int64)
+            y.t.fill_(0)
+            L.call("nirgan_conv_igemm", C.byref(d), None)
+            bad += (y.t != first).any().to(torch.int64)
         assert int(bad.item()) == 0, f"{case}: {int(bad.item())} of {100 * SOAK} launches differ"

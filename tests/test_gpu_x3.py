@@ -326,3 +326,30 @@ def test_four_wave_plane_gemm_is_bitwise_the_eight_wave_plane_gemm(shape):
     assert torch.equal(outs[0], outs[L.W6_X3_R4])
     ref = torch.bmm(V.view(64, T, Cc).double(), U.view(64, K, Cc).double().transpose(1, 2)).reshape(-1)
     assert _err(outs[L.W6_X3_R4], ref)[0] < 2e-6
+
+
+def test_plane_gemm_the_four_wave_tile_cannot_take_runs_and_is_named_on_the_eight_wave_tile():
+    """NIRGAN_W6_X3_R4 on planes of C = 64 (two K-tiles per item: the four-wave tile needs three, igemm_x3r.h::conv_x3r_ok): the launch
+    runs the eight-wave tile, the name query says so, and the output is bitwise that of algo = 0"""
+    B, H, W, Cc, K = 2, 16, 16, 64, 128
+    g = torch.Generator().manual_seed(23)
+    T = B * ((H + 5) // 6) * ((W + 5) // 6)
+    V = torch.randn(64 * T * Cc, generator=g).to(DEV)
+    U = (torch.randn(64 * K * Cc, generator=g) * 0.05).to(DEV)
+    zero = torch.zeros(64, device=DEV)
+    plane = 64 * K * Cc
+    U3 = torch.zeros(3 * plane, dtype=torch.bfloat16, device=DEV)
+    L.call("nirgan_split3", U.data_ptr(), U3.data_ptr(), plane, plane, None)
+    outs = {}
+    for algo in (0, L.W6_X3_R4):
+        M = torch.full((64 * T * K,), float("nan"), device=DEV)
+        d = L.Wino6Desc()
+        d.r, d.B, d.H, d.W, d.C, d.K = 6, B, H, W, Cc, K
+        d.U3, d.V, d.V_elems, d.M, d.M_elems, d.zero_page = U3.data_ptr(), V.data_ptr(), V.numel(), M.data_ptr(), M.numel(), zero.data_ptr()
+        d.algo = algo
+        assert L.backend().nirgan_wino6_gemm_kernel_name(C.byref(d)) == b"conv_x3_kernel<128> (planes)"
+        L.call("nirgan_wino6_gemm", C.byref(d), None)
+        torch.cuda.synchronize()
+        outs[algo] = M
+    assert torch.isfinite(outs[0]).all()
+    assert torch.equal(outs[0], outs[L.W6_X3_R4])

@@ -976,3 +976,27 @@ def test_paired_sub_pixel_phases_keep_the_step(emu, monkeypatch):
     assert ((gG - gG4).norm() / gG4.norm()).item() < 1e-5 and ((gD - gD4).norm() / gD4.norm()).item() < 1e-5
     o = O.OracleTrainer(G0, D0, 6).step(rgb, nir)
     close(out["loss_G"], o["loss_G"], 1e-5, "loss_G against the oracle")
+
+
+def test_emulator_rejects_retired_algo_values(emu):
+    """the emulator refuses the algo values the library no longer has (as the library does: NIRGAN_ERR_ARG, nothing computed), and
+    accepts the ones it keeps"""
+    import ctypes as C
+    from emu_backend import CONV_ALGOS, W6_ALGOS, WGRAD_ALGOS
+    assert CONV_ALGOS == (0, L.CONV_TILE128, L.CONV_X3_R4) and WGRAD_ALGOS == (0, L.WGRAD_ONE_UNIT, L.WGRAD_TILE128)
+    assert W6_ALGOS == (0, L.W6_ONE_TILE, L.W6_DIRECT_TILE, L.W6_X3_R4, L.W6_PATCH_PER_THREAD, L.W6_PATCH_PER_LANES)
+    c, w, d = L.ConvDesc(), L.WgradDesc(), L.Wino6Desc()
+    for a in (2, 3):
+        c.algo = a
+        assert emu.nirgan_conv_igemm(C.byref(c)) == -1 and b"algo" in emu.nirgan_last_error()
+        assert emu.nirgan_conv_igemm_group([C.pointer(c)], 1) == -1 and b"algo" in emu.nirgan_last_error()
+    c.algo = 0
+    w.algo = 3
+    assert emu.nirgan_wgrad_igemm(C.byref(w)) == -1 and b"algo" in emu.nirgan_last_error()
+    assert emu.nirgan_conv_wgrad_pair(C.byref(c), C.byref(w)) == -1 and b"algo" in emu.nirgan_last_error()
+    assert emu.nirgan_wino6_gemm_wgrad_pair(C.byref(d), C.byref(w)) == -1 and b"algo" in emu.nirgan_last_error()
+    for a in (2, 4):
+        d.algo = a
+        for f in (emu.nirgan_wino6_input, emu.nirgan_wino6_gemm, emu.nirgan_wino6_output):
+            assert f(C.byref(d)) == -1 and b"algo" in emu.nirgan_last_error(), f
+        assert emu.nirgan_wino6_input_norm(C.byref(d), 0, 0, 0, 0, 0.0) == -1 and b"algo" in emu.nirgan_last_error()
