@@ -136,7 +136,9 @@ typedef struct {
     int out_span;
 } nirgan_conv_desc;
 #define NIRGAN_CONV_TILE128 1
-#define NIRGAN_CONV_X3_R4 4     /* precision 3, N % 128 == 0: the four-wave register-fed tile of igemm_x3r.h instead of the eight-wave tile (A/B; same output bits) */
+#define NIRGAN_CONV_X3_R4 4     /* precision 3, N % 128 == 0: the four-wave register-fed tile of igemm_x3r.h instead of the eight-wave tile (A/B; same output bits).
+                                 * Taken where it applies: OW >= 16, B OH OW < 2^24 and out_elems <= 2^30 (its stores address the output with 32-bit byte
+                                 * offsets; for the Winograd plane batches, per plane); other launches run on the eight-wave tile. */
 
 int nirgan_conv_igemm(const nirgan_conv_desc* d, void* stream);
 

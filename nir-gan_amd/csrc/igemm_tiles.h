@@ -91,6 +91,7 @@ struct ConvParams {
     const unsigned short* w3;  // precision 3: the packed weights as three bf16 planes h, m, l (nirgan_split3), w3_plane elements apart
     long long w3_plane;
     int ch;                    // channels per output pixel: N, or N / 2 with nirgan_conv_desc.out_span = 2 (conv_x3_persist only)
+    long long out_elems;       // floats the launch may address from `out` (per plane for the Winograd plane batches): igemm_x3r.h::conv_x3r_ok
 };
 
 
@@ -1329,6 +1330,7 @@ inline int build_conv_params(const nirgan_conv_desc* d, ConvParams& p) {
     p.ntaps = d->ntaps;
     for (int t = 0; t < NIRGAN_MAX_TAPS; ++t) p.tap_off[t] = t < d->ntaps ? d->tap_dh[t] * p.in_row + d->tap_dw[t] * d->in_cs : 0;
     p.K = d->ntaps * d->run;
+    p.out_elems = d->out_elems;
     p.out_cs = d->out_cs; p.out_row = d->out_wp * d->out_cs; p.out_img = d->out_hp * p.out_row;
     p.out_stride = d->out_stride; p.out_org = d->out_oh * p.out_row + d->out_ow * d->out_cs;
     p.OW = d->OW; p.OHW = d->OH * d->OW;

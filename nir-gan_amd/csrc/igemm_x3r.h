@@ -745,8 +745,10 @@ __device__ __forceinline__ void conv_x3r_persist(const NG_CONST X3Work* const wp
         constexpr unsigned HALF = 16 * BN * 4;
         const char* const obase = ng_uniform_ptr(reinterpret_cast<const char*>(E.out));
         // byte steps of the row walk: RPP pixels on; a row wrap; a sample wrap
-        const int d0 = RPP * e.out_px * 4, dW = (e.out_row - e.OW * e.out_px) * 4, dH = (e.out_img - e.OH * e.out_row) * 4;
-        int off = (e.b * e.out_img + e.oh * e.out_row + e.ow * e.out_px + e.out_org + e.n) * 4;
+        // (32-bit BYTE offsets from the scalar base, unsigned: host -- the output spans < 2^32 bytes, conv_x3r_ok -- so 2^31 .. 2^32 - 1 is
+        // defined; element offsets are < 2^31)
+        const unsigned d0 = unsigned(RPP * e.out_px) * 4u, dW = unsigned(e.out_row - e.OW * e.out_px) * 4u, dH = unsigned(e.out_img - e.OH * e.out_row) * 4u;
+        unsigned off = unsigned(e.b * e.out_img + e.oh * e.out_row + e.ow * e.out_px + e.out_org + e.n) * 4u;
         // (uniform) the column of the slice's first row: the slice wraps iff its 16 rows cross the end of an image row
         int s_ow = __builtin_amdgcn_readfirstlane(e.ow);       // (lane 0 stands on the slice's first row)
         const int s_OW = e.OW;
@@ -768,7 +770,7 @@ __device__ __forceinline__ void conv_x3r_persist(const NG_CONST X3Work* const wp
         // path each move 32 KB per wave and slice -- back to back they add up, alternating they overlap
         // the byte offsets of a slice's eight row segments (in front of the slice's reads: nothing but the wait stands between the reads
         // and the stores -- and no branch, which scripts/check_x3_asm.py's linear walk could not follow)
-        auto Aoff = [&](int (&ooff)[SP]) __attribute__((always_inline)) {
+        auto Aoff = [&](unsigned (&ooff)[SP]) __attribute__((always_inline)) {
             if (s_ow + 16 <= s_OW) {
                 // the slice stays inside one image row: the lane's rows are d0 bytes apart
 #pragma unroll
@@ -804,7 +806,7 @@ __device__ __forceinline__ void conv_x3r_persist(const NG_CONST X3Work* const wp
                 s_ow -= s_ow >= s_OW ? s_OW : 0;    // (host: OW >= 16 for this kernel's problems, see conv_x3r_ok)
             }
         };
-        auto S = [&](auto next_tag, f32x4 (&vv)[SP], const int (&ooff)[SP]) __attribute__((always_inline)) {
+        auto S = [&](auto next_tag, f32x4 (&vv)[SP], const unsigned (&ooff)[SP]) __attribute__((always_inline)) {
             constexpr int NEXT = decltype(next_tag)::value;
             // the slice's reads have landed (behind them at most the 16 stores of the next slice's W: lgkmcnt counts to 15, the LDS
             // pipe returns in order -- all but the 15 youngest done means every read done)
@@ -827,7 +829,7 @@ __device__ __forceinline__ void conv_x3r_persist(const NG_CONST X3Work* const wp
             static_assert(SP == NT, "one column block of the next slice per store");
 #pragma unroll
             for (int pass = 0; pass < SP; ++pass) {
-                const unsigned oo = unsigned(ooff[pass]);
+                const unsigned oo = ooff[pass];
                 if (!(NG_X3R_KO & 64)) asm volatile("global_store_dwordx4 %1, %0, %2" : "+v"(vv[pass]) : "v"(oo), "s"(ob) : "memory");
                 if constexpr (NEXT < 4) stage_w(next_tag, pass);
             }
@@ -839,7 +841,7 @@ __device__ __forceinline__ void conv_x3r_persist(const NG_CONST X3Work* const wp
         using J4 = std::integral_constant<int, 4>;
         // (slice 0 is in the staging block already: written in front of the epilogue's set-up, whose ~400 cycles of address arithmetic and
         // scalar loads then run beside the LDS writes)
-        int oo[SP];
+        unsigned oo[SP];
         Aoff(oo); R(J0{}, v0); S(J1{}, v0, oo);             // (the reads are waited for with lgkmcnt(0): nothing is behind them yet)
         Aoff(oo); R(J1{}, v1); S(J2{}, v1, oo);
         // the item behind the next one is looked up and its loader state prepared HERE: ~1 100 cycles, most of them latency of dependent
@@ -1150,9 +1152,13 @@ inline bool conv_x3r_stats(const ConvParams& p) { return p.stats != nullptr; }
 #ifndef NG_X3R_GEN_MIN_NK
 #define NG_X3R_GEN_MIN_NK 24
 #endif
+// The full tiles' plain epilogue stores through 32-bit BYTE offsets from the output base (epilogue_full): the output the launch addresses
+// must span < 2^32 bytes (larger outputs take the eight-wave tile, the same bits); split_row divides by a float reciprocal, exact for
+// row numbers below 2^24.
 inline bool conv_x3r_ok(const ConvParams& p, const int bn) {
     const int nk = p.ntaps * (p.run >> 5);
-    return bn == 128 && p.algo == NIRGAN_CONV_X3_R4 && p.OW >= 16 && nk >= (conv_x3r_generic(p) ? NG_X3R_GEN_MIN_NK : 3);
+    return bn == 128 && p.algo == NIRGAN_CONV_X3_R4 && p.OW >= 16 && nk >= (conv_x3r_generic(p) ? NG_X3R_GEN_MIN_NK : 3)
+           && p.out_elems * 4 <= (1ll << 32) && p.M < (1 << 24);
 }
 
 }  // namespace ng
