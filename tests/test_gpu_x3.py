@@ -91,41 +91,65 @@ def test_conv_x3_against_float64_at_the_fp32_tiles_error(case):
     assert e3[0] <= 2.0 * e0[0] + 2e-7 and e3[1] <= 2.0 * e0[1] + 5e-8, (e0, e3)
 
 
-WGRADS = [  # B, H, cin, cout, k, stride
-    (2, 64, 64, 128, 3, 2),        # N = 128, K = 576: a partly filled fifth column tile
-    (2, 64, 128, 256, 3, 2),       # N = 256: 256-row units (OW = 32: the scalar pixel walk needs whole 32-pixel K-tiles per image row)
-    (4, 64, 64, 128, 4, 2),        # K = 1024
+WGRADS = [  # kind, B, H, cin, cout, k, stride, the route of the precision-3 launch
+    ("conv", 2, 64, 64, 128, 3, 2, "wgrad_x3_kernel<"),      # N = 128, K = 576: a partly filled fifth column tile
+    ("conv", 2, 64, 128, 256, 3, 2, "wgrad_x3_kernel<"),     # N = 256: 256-row units (OW = 32: the scalar pixel walk needs whole 32-pixel K-tiles per image row)
+    ("conv", 4, 64, 64, 128, 4, 2, "wgrad_x3_kernel<"),      # K = 1024
+    # the generator's layers at the padded width of the YAML default (padding: 10, 276 x 276 tiles), B = 16: OW = 138 and 69 are not
+    # whole 32-pixel K-tiles, so both precisions run on the exact-fp32 tile today
+    ("conv", 16, 276, 64, 128, 3, 2, "wgrad_igemm_kernel<128>"),     # Conv2d(64, 128, 3, s2) 276 -> 138
+    ("conv", 16, 138, 128, 256, 3, 2, "wgrad_igemm_kernel<128>"),    # Conv2d(128, 256, 3, s2) 138 -> 69
+    ("convT", 16, 69, 256, 128, 3, 2, "wgrad_igemm_kernel<128>"),    # ConvTranspose2d(256, 128, 3, s2) 69 -> 138: rows = input channels
+    ("convT", 16, 138, 128, 64, 3, 2, "wgrad_igemm_kernel<128>"),    # ConvTranspose2d(128, 64, 3, s2) 138 -> 276
 ]
+# the exact-fp32 tile's own error against float64 (rms over the gradient, relative to its largest element): fp32 summation of
+# rows_per_split products per slab, then of nsplit slabs.  Measured 3e-8 to 4e-8 on the B <= 4 cases and 1.9e-7 to 2.4e-7 on the B = 16
+# layers; a gradient that lost a pixel or read a shifted window is off by about 1e-3
+WGRAD_EXACT_RMS = 6e-7
 
 
 @pytest.mark.parametrize("case", WGRADS)
 def test_wgrad_x3_against_float64_at_the_fp32_tiles_error(case, monkeypatch):
-    B, H, cin, cout, k, s = case
+    kind, B, H, cin, cout, k, s, x3_route = case
     g = torch.Generator().manual_seed(12)
     ctx = Ctx(DEV)
-    OH = G.conv_out(H, k, s, 1)
-    x = Halo(ctx, B, H, H, cin, 1)
-    x.interior().copy_(torch.randn(B, H, H, cin, generator=g).to(DEV))
-    dy = Halo(ctx, B, OH, OH, cout, 0)
-    dy.t.copy_(torch.randn(B, OH, OH, cout, generator=g).to(DEV))
-    spec = G.conv_fwd_pack(cout, cin, k)
+    if kind == "conv":      # p = dY (rows = output channels), q = X gathered with stride s
+        OH = G.conv_out(H, k, s, 1)
+        x = Halo(ctx, B, H, H, cin, 1)
+        x.interior().copy_(torch.randn(B, H, H, cin, generator=g).to(DEV))
+        dy = Halo(ctx, B, OH, OH, cout, 0)
+        dy.t.copy_(torch.randn(B, OH, OH, cout, generator=g).to(DEV))
+        spec, taps, N, P, Q, OW, p_oh, q_oh = G.conv_fwd_pack(cout, cin, k), G.conv_fwd_taps(k, cin), cout, dy, x, OH, 0, 0
+    else:                   # ConvTranspose2d(cin, cout, k, 2, padding 1, output_padding 1): p = X (rows = input channels), q = dY with stride 2
+        x = Halo(ctx, B, H, H, cin, 1)
+        x.interior().copy_(torch.randn(B, H, H, cin, generator=g).to(DEV))
+        dy = Halo(ctx, B, 2 * H, 2 * H, cout, 1)
+        dy.interior().copy_(torch.randn(B, 2 * H, 2 * H, cout, generator=g).to(DEV))
+        spec, taps, N, P, Q, OH, OW, p_oh, q_oh = G.convT_dgrad_pack(cin, cout, k), G.convT_dgrad_taps(k, cout), cin, x, dy, H, H, 1, 0
     got = {}
     for prec in (0, 3):
         monkeypatch.setattr(OPT, "split3", prec == 3)
-        gw = ctx.zeros(cout, cin, k, k)
+        gw = ctx.zeros(cin, cout, k, k) if kind == "convT" else ctx.zeros(cout, cin, k, k)
         ctx.keep.append(gw)
         plan = Plan(ctx)
-        d = emit_wgrad(plan, ctx, dy, x, G.conv_fwd_taps(k, cin), spec, gw, N=cout, OH=OH, OW=OH, p_oh=0, p_ow=0, q_stride=s, q_oh=0, q_ow=0)
-        assert d.precision == prec
-        if prec == 3:
-            assert L.backend().nirgan_wgrad_kernel_name(C.byref(d)).startswith(b"wgrad_x3_kernel")
+        d = emit_wgrad(plan, ctx, P, Q, taps, spec, gw, N=N, OH=OH, OW=OW, p_oh=p_oh, p_ow=p_oh, q_stride=s, q_oh=q_oh, q_ow=q_oh)
+        name = L.backend().nirgan_wgrad_kernel_name(C.byref(d)).decode()
+        assert name.startswith(x3_route if prec == 3 else "wgrad_igemm_kernel<"), name
+        assert d.precision == (prec if x3_route.startswith("wgrad_x3") else 0)
         plan.run()
         torch.cuda.synchronize()
         got[prec] = gw.clone()
-    xd, dyd = x.t.double(), dy.t.double().reshape(-1, cout)
-    ref = torch.stack([torch.stack([dyd.T @ xd[:, kh:kh + (OH - 1) * s + 1:s, kw:kw + (OH - 1) * s + 1:s, :].reshape(-1, cin) for kw in range(k)], -1)
-                       for kh in range(k)], -2)
+    if kind == "conv":
+        xd, dyd = x.t.double(), dy.t.double().reshape(-1, cout)
+        ref = torch.stack([torch.stack([dyd.T @ xd[:, kh:kh + (OH - 1) * s + 1:s, kw:kw + (OH - 1) * s + 1:s, :].reshape(-1, cin) for kw in range(k)], -1)
+                           for kh in range(k)], -2)
+    else:                   # gw[ci][co][kh][kw] = sum X[b][iy][ix][ci] dY[b][2 iy - 1 + kh][2 ix - 1 + kw][co] (dY's zero halo of 1)
+        xd, dyd = x.interior().double().reshape(-1, cin), dy.t.double()
+        ref = torch.stack([torch.stack([xd.T @ dyd[:, kh:kh + 2 * (H - 1) + 1:2, kw:kw + 2 * (H - 1) + 1:2, :].reshape(-1, cout) for kw in range(k)], -1)
+                           for kh in range(k)], -2)
     e0, e3 = _err(got[0], ref), _err(got[3], ref)
+    print(f"\n{kind} B {B} {H}^2 {cin}->{cout}: exact tile (max, rms) {e0[0]:.3g} {e0[1]:.3g}, precision 3 {e3[0]:.3g} {e3[1]:.3g}")
+    assert e0[1] <= WGRAD_EXACT_RMS, e0
     # (the split tile runs one unit per CU: up to twice the pixels per split of the exact tile's launch, i.e. longer fp32 accumulation
     # chains -- sqrt(2) of its summation noise on top of the products')
     assert e3[0] <= 2.0 * e0[0] + 2e-7 and e3[1] <= 2.5 * e0[1] + 5e-8, (e0, e3)
