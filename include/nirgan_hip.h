@@ -411,6 +411,42 @@ typedef struct {
 int nirgan_pix_loss(const nirgan_pix_loss_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-pixel baseline models, fused (csrc/pixmlp.hip).  rgb [B][3][H][W], nir / pred / dpred [B][1][H][W], fp32 NCHW, contiguous.
+ *   hidden = 0   Linear_NIR: y = w . x + b                                    model/baseline_models.py:17-30
+ *   hidden = 64  MLP_NIR:    y = W3 . relu(W2 . relu(W1 . x + b1) + b2) + b3   model/baseline_models.py:80-100
+ * `params` / `grads` are the network's flat fp32 ranges (state_dict order, every tensor padded to a multiple of 4 floats:
+ * 8 floats for hidden = 0, 4484 for hidden = 64), read and written in place.
+ *   fwd:   pred = model(rgb).
+ *   train: ONE pass over the pixels: prediction (stored when `pred` is set, bitwise the forward entry's), then
+ *            loss_out[0] += mean((pred - nir)^2)            (ACCUMULATED, like the sums of the pixel-loss entry: the caller zeroes it)
+ *            grads[0..P)  = d mean((pred - nir)^2) / d params   (OVERWRITTEN, padding elements = 0)
+ *          (F.mse_loss + backward, baseline_models.py:28, :98).  With `dpred` set (the autograd bridge: an upstream gradient with
+ *          respect to the prediction) dy is read from it instead of 2 (pred - nir) / n; nir and loss_out are then not touched.
+ *          Persistent workgroups leave one record [P + 4] each in `ws`; a second launch adds the records in workgroup order.  No
+ *          float atomics, the grid is a function of the shape only: two runs are bitwise equal.  The grid's cap is a CONSTANT of this
+ *          gfx950-only library (hidden = 64: 256 workgroups, one per CU of the MI355X; hidden = 0: 2048), not a device query: the
+ *          entries keep no state and the ws_elems query needs no device.  The hidden activations never
+ *          reach HBM.  `ws` holds grid x record floats, independent of the pixel count once the tiles outnumber the grid.
+ * Any B, H, W >= 1 with B*H*W < 2^31 (partial tiles are predicated).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* rgb;
+    const float* nir;                     /* train: the target; NULL with dpred, and for fwd */
+    const float* dpred;                   /* train: NULL, or d loss / d pred given from outside */
+    int B, H, W;
+    int hidden;                           /* 0 or 64; anything else fails with NIRGAN_ERR_ARG */
+    const float* params;
+    float* grads;                         /* train; NULL for fwd */
+    float* pred;                          /* fwd: required; train: optional */
+    float* loss_out;                      /* train without dpred: one float, accumulated */
+    float* ws; int64_t ws_elems;          /* train: >= the ws_elems query below; not shared between streams */
+} nirgan_pixmlp_desc;
+#define NIRGAN_PIXMLP_TILE 32             /* pixels per wave tile of the hidden = 64 kernels (hidden = 0: 256 per workgroup) */
+int nirgan_pixmlp_fwd(const nirgan_pixmlp_desc* d, void* stream);
+int nirgan_pixmlp_train(const nirgan_pixmlp_desc* d, void* stream);
+int64_t nirgan_pixmlp_ws_elems(int B, int H, int W, int hidden);
+
+/* ---------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam, amsgrad=False, weight_decay=0) on a flat fp32 range.
  * model/pix2pix.py:486-487.  `step` is the 1-based count after increment.
  * ------------------------------------------------------------------------------------- */

@@ -30,11 +30,62 @@ def _rank_mean(value: float, device) -> float:
     return value
 
 
+def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from):
+    """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
+    (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
+    if reducer is not None:
+        raise NotImplementedError("data-parallel training of the baseline models is not on the MI355X path")
+    optim = model.configure_optimizers()
+    history = {"train": [], "val": [], "lr": []}
+    step, first_epoch = 0, 0
+    if resume_from is not None:
+        ck = torch.load(resume_from, map_location=device, weights_only=False)
+        model.load_state_dict(ck["state_dict"], strict=True)
+        model._flat().touch()
+        if "optimizer_states" in ck:
+            optim.load_state_dict(ck["optimizer_states"][0])
+            model.lr = optim.param_groups[0]["lr"]
+        step, first_epoch = int(ck.get("global_step", 0)), int(ck.get("epoch", -1)) + 1
+    for epoch in range(first_epoch, max_epochs):
+        model.train()
+        for batch in train_loader:
+            view = model.train_batch(_to_device(batch, device))
+            if log_every and step % log_every == 0:          # reading the loss synchronises: not every step
+                rec = {"epoch": epoch, "step": step, **view.as_dict()}
+                history["train"].append(rec)
+                if on_log:
+                    on_log(rec)
+            step += 1
+        if val_loader is not None:
+            model.eval()
+            sums, n = {}, 0
+            for i, batch in enumerate(val_loader):
+                model.logged.clear()
+                model.validation_step(_to_device(batch, device), i)
+                for k, v in model.logged.items():
+                    if k.startswith("val/"):
+                        sums[k] = sums.get(k, 0.0) + float(v)
+                n += 1
+            val = {k: v / max(n, 1) for k, v in sums.items()}
+            val["epoch"] = epoch
+            history["val"].append(val)
+            if on_log:
+                on_log(val)
+        history["lr"].append({"epoch": epoch, "lr": model.lr})
+        if ckpt_path is not None:
+            torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(),
+                        "optimizer_states": [optim.state_dict()], "lr_schedulers": []}, ckpt_path)
+    return history
+
+
 def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]] = None, *, max_epochs: int = 1,
         device=None, reducer=None, log_every: int = 10, on_log: Optional[Callable[[Dict[str, float]], None]] = None,
         ckpt_path: Optional[str] = None, resume_from: Optional[str] = None) -> Dict[str, list]:
-    """Train ``model`` (model.pix2pix.Px2Px_PL).  Returns the history {'train': [...], 'val': [...], 'lr': [...]}."""
+    """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
+    {'train': [...], 'val': [...], 'lr': [...]}."""
     device = device or next(model.parameters()).device
+    if getattr(model, "is_pixel_baseline", False):
+        return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from)
     trainer = model.fused_trainer(reducer=reducer)
     (optim_d, optim_g), scheds = model.configure_optimizers()
     sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]

@@ -93,6 +93,14 @@ class PixLossDesc(C.Structure):
                 ("sums", fp), ("grad_pred", fp), ("ws", fp), ("ws_elems", i64)]
 
 
+PIXMLP_TILE = 32                # include/nirgan_hip.h: NIRGAN_PIXMLP_TILE
+
+
+class PixMlpDesc(C.Structure):
+    _fields_ = [("rgb", fp), ("nir", fp), ("dpred", fp), ("B", i32), ("H", i32), ("W", i32), ("hidden", i32),
+                ("params", fp), ("grads", fp), ("pred", fp), ("loss_out", fp), ("ws", fp), ("ws_elems", i64)]
+
+
 class InjectFwdDesc(C.Structure):
     _fields_ = [("z", fp), ("e", fp), ("scale", fp), ("style", i32), ("B", i32), ("H", i32), ("W", i32), ("C", i32),
                 ("out", fp), ("o_hp", i32), ("o_wp", i32), ("o_pad", i32)]
@@ -223,6 +231,9 @@ PROTOTYPES = {
     "nirgan_endconv_wgrad": (i32, [C.POINTER(EndConvDesc), fp]),
     "nirgan_lsgan": (i32, [fp, i64, f32, f32, fp, fp, fp]),
     "nirgan_pix_loss": (i32, [C.POINTER(PixLossDesc), fp]),
+    "nirgan_pixmlp_fwd": (i32, [C.POINTER(PixMlpDesc), fp]),
+    "nirgan_pixmlp_train": (i32, [C.POINTER(PixMlpDesc), fp]),
+    "nirgan_pixmlp_ws_elems": (i64, [i32, i32, i32, i32]),
     "nirgan_adam": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, f32, i32, fp]),
     "nirgan_bilinear_fwd": (i32, [fp, i32, i32, i32, fp, i32, i32, fp]),
     "nirgan_bilinear_bwd": (i32, [fp, i32, i32, i32, fp, i32, i32, fp]),
