@@ -476,6 +476,39 @@ int64_t nirgan_image_metrics_ws_elems(int planes, int H, int W);
 int nirgan_image_metrics(const nirgan_metrics_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Per-tile validation metrics: the rows of the reference's results table (validation_utils/get_results_table.py:59-94 and
+ * validation_utils/spider_validation_callback.py:28-64, batch size 1 on CPU copies there), ONE device pass for a whole batch.
+ * Per tile b, over the evaluation window [y0, y0+ch) x [x0, x0+cw) of the stored images (the reference's
+ * crop_center(.., 240), validation_utils/val_utils.py:20-42, by indexing instead of by copying):
+ *   rows[b][0] l1    = mean |nir - pred|                      rows[b][1] l2 = mean (nir - pred)^2
+ *   rows[b][2] ssim  = mean of the SSIM map of (nir, pred), formula above; the Gaussian filter reflects at the border of the
+ *                      WINDOW (kornia pads the crop), pixels outside the window are never read
+ *   rows[b][3] psnr  = 10 log10(max_val^2 / l2), +inf where l2 == 0 (kornia.metrics.psnr)
+ *   rows[b][4..6]    = mean |idx(pred) - idx(nir)| for NDVI, NDWI, EVI: the 'logging_dict' errors of RemoteSensingIndices with
+ *                      criterion l1, formulas and epsilons of the pixel-loss entry above.  rgb == NULL: these three stay untouched
+ *   rows[b][7..8]    = mean of nir / of pred over the patch x patch square at (ch/2 - patch/2, cw/2 - patch/2) of the window
+ *                      (validation_utils/time_series_validation.py:120-132).  patch == 0: these two stay untouched
+ * Every computed column is OVERWRITTEN.  ws: at least the _ws_elems count of floats.  Deterministic: a tile's reduction order depends
+ * only on (ch, cw), so its row is bitwise the same alone and inside any batch (fixed-order partial sums, no float atomics).
+ * Argument errors (null pointer, window outside the image, ch or cw <= window/2, even window or > 11, patch > ch or cw,
+ * workspace too small) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_TILE_METRIC_COLS 9   /* l1, l2, ssim, psnr, l1_ndvi, l1_ndwi, l1_evi, patch_mean_nir, patch_mean_pred */
+typedef struct {
+    const float* rgb;          /* [B][3][H][W] fp32 NCHW, may be NULL: index columns are then not computed */
+    const float* nir;          /* [B][1][H][W] */
+    const float* pred;         /* [B][1][H][W] */
+    int B, H, W;
+    int y0, x0, ch, cw;        /* evaluation window inside each image (crop_center: y0 = (H-ch)/2, x0 = (W-cw)/2) */
+    int window; float sigma, max_val, eps;   /* SSIM: odd window <= 11, kornia defaults 1.5 / 1.0 / 1e-12 */
+    int patch;                 /* side of the centred patch whose nir / pred means are reported; 0 = none */
+    float* ws; int64_t ws_elems;
+    float* rows;               /* [B][NIRGAN_TILE_METRIC_COLS] on device, OVERWRITTEN */
+} nirgan_tile_metrics_desc;
+int64_t nirgan_tile_metrics_ws_elems(int B, int ch, int cw);
+int nirgan_tile_metrics(const nirgan_tile_metrics_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * SSIM term of the generator objective, value AND gradient: model/pix2pix.py:233-237 adds
  * lambda_ssim * ssim_loss(pred, nir); utils/losses.py:10-30: 1 - kornia.metrics.ssim(img1, img2, window_size=11).mean()
  * (Gaussian window sigma 1.5, reflect border, max_val 1, eps 1e-12 in the denominator).

@@ -8,7 +8,9 @@ reference's keys (train.py:61-65 / create_synthetic_dataset.py:24-26 load it wit
 (both Adams: moments and step counts, torch.optim.Adam's format) and ``lr_schedulers`` (both ReduceLROnPlateau), so that
 ``resume_from`` continues a run the way ``Trainer(resume_from_checkpoint=...)`` does (train.py:66-70,126).  Loggers, wandb, image plots and
 callbacks are out of scope.  Data parallel: pass a ``parallel.GradReducer`` (one process per GPU, RCCL); validation
-metrics are averaged over ranks when a process group is initialised.
+metrics are averaged over ranks when a process group is initialised.  ``tile_table_path``: every validation epoch also
+writes the per-tile metrics table of its validation batches (validation_utils.tile_metrics.evaluate_tiles, the reference's
+spider_validation_callback) to ``<stem>_e<epoch><ext>``; rank 0 writes it under data parallel.
 """
 from __future__ import annotations
 
@@ -30,7 +32,15 @@ def _rank_mean(value: float, device) -> float:
     return value
 
 
-def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from):
+def _write_tile_table(model, val_loader, device, path, crop, epoch):
+    import os
+    from validation_utils.tile_metrics import evaluate_tiles
+    stem, ext = os.path.splitext(path)
+    evaluate_tiles(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
+
+
+def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
+                  tile_table_path=None, tile_table_crop=240):
     """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
     (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
     if reducer is not None:
@@ -71,6 +81,8 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
             history["val"].append(val)
             if on_log:
                 on_log(val)
+            if tile_table_path is not None:
+                _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
         history["lr"].append({"epoch": epoch, "lr": model.lr})
         if ckpt_path is not None:
             torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(),
@@ -80,12 +92,15 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
 
 def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]] = None, *, max_epochs: int = 1,
         device=None, reducer=None, log_every: int = 10, on_log: Optional[Callable[[Dict[str, float]], None]] = None,
-        ckpt_path: Optional[str] = None, resume_from: Optional[str] = None) -> Dict[str, list]:
+        ckpt_path: Optional[str] = None, resume_from: Optional[str] = None, tile_table_path: Optional[str] = None,
+        tile_table_crop: Optional[int] = 240) -> Dict[str, list]:
     """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
-    {'train': [...], 'val': [...], 'lr': [...]}."""
+    {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
+    per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles)."""
     device = device or next(model.parameters()).device
     if getattr(model, "is_pixel_baseline", False):
-        return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from)
+        return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
+                             tile_table_path, tile_table_crop)
     trainer = model.fused_trainer(reducer=reducer)
     (optim_d, optim_g), scheds = model.configure_optimizers()
     sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
@@ -133,6 +148,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
                 sched_d.step(val[monitor])
                 sched_g.step(val[monitor])
                 trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
+            if tile_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
+                _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
         history["lr"].append({"epoch": epoch, "lr_d": trainer.lr if trainer.lr_d is None else trainer.lr_d,
                               "lr_g": trainer.lr if trainer.lr_g is None else trainer.lr_g})
         if ckpt_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):

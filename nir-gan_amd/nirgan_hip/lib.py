@@ -118,6 +118,16 @@ class MetricsDesc(C.Structure):
                 ("ws", fp), ("ws_elems", i64), ("means", fp)]
 
 
+TILE_METRIC_COLS = 9            # include/nirgan_hip.h: NIRGAN_TILE_METRIC_COLS
+
+
+class TileMetricsDesc(C.Structure):
+    _fields_ = [("rgb", fp), ("nir", fp), ("pred", fp), ("B", i32), ("H", i32), ("W", i32),
+                ("y0", i32), ("x0", i32), ("ch", i32), ("cw", i32),
+                ("window", i32), ("sigma", f32), ("max_val", f32), ("eps", f32), ("patch", i32),
+                ("ws", fp), ("ws_elems", i64), ("rows", fp)]
+
+
 class SsimLossDesc(C.Structure):
     _fields_ = [("pred", fp), ("target", fp), ("planes", i32), ("H", i32), ("W", i32), ("window", i32), ("sigma", f32), ("max_val", f32),
                 ("eps", f32), ("weight", f32), ("ws", fp), ("ws_elems", i64), ("loss", fp), ("value", fp), ("grad_pred", fp)]
@@ -212,6 +222,8 @@ PROTOTYPES = {
     "nirgan_hist_match": (i32, [C.POINTER(HistMatchDesc), fp]),
     "nirgan_image_metrics_ws_elems": (i64, [i32, i32, i32]),
     "nirgan_image_metrics": (i32, [C.POINTER(MetricsDesc), fp]),
+    "nirgan_tile_metrics_ws_elems": (i64, [i32, i32, i32]),
+    "nirgan_tile_metrics": (i32, [C.POINTER(TileMetricsDesc), fp]),
     "nirgan_ssim_loss_ws_elems": (i64, [i32, i32, i32, i32]),
     "nirgan_ssim_loss": (i32, [C.POINTER(SsimLossDesc), fp]),
     "nirgan_emd_loss_ws_bytes": (i64, [i32, i64, i32]),

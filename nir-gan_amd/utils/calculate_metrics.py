@@ -6,6 +6,10 @@
 The reference moves both tensors to the CPU every 10th batch for this (model/pix2pix.py:183-186); here it is ONE
 fused pass on the device (nirgan_image_metrics).  ``image_metrics_device`` returns the three means as a device
 tensor without synchronising, for callers that log asynchronously.
+
+``tile_metrics_device(rgb, nir, pred, crop, ..)`` is the per-tile form behind the validation table
+(validation_utils/): one row of ``TILE_METRIC_COLUMNS`` per tile of the batch in ONE fused pass (nirgan_tile_metrics),
+the centre crop applied by indexing.
 """
 import ctypes as C
 import math
@@ -49,3 +53,42 @@ def calculate_metrics(pred, target, phase="train"):
         phase + '/PSNR': psnr,
         phase + '/SSIM': ssim,
     }
+
+
+# column order of nirgan_tile_metrics rows (include/nirgan_hip.h)
+TILE_METRIC_COLUMNS = ("l1", "l2", "ssim", "psnr", "l1_ndvi", "l1_ndwi", "l1_evi", "patch_mean_nir", "patch_mean_pred")
+assert len(TILE_METRIC_COLUMNS) == L.TILE_METRIC_COLS
+
+
+def tile_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, window_size: int = 11, patch: int = 32,
+                        max_val: float = 1.0, sigma: float = 1.5, eps: float = 1e-12) -> torch.Tensor:
+    """One row of ``TILE_METRIC_COLUMNS`` per tile: a ``B x 9`` fp32 tensor on the inputs' device, no host sync.
+
+    ``nir`` / ``pred`` are [B, 1, H, W], ``rgb`` [B, 3, H, W] (more bands are cut to the first three) or ``None``: the three
+    index columns are then NaN.  ``crop`` is the side of the centred evaluation window (the reference's
+    ``crop_center(.., 240)``; ``None`` = the whole image): SSIM reflects at the window's border, exactly as on a cropped copy,
+    but nothing is copied.  ``patch`` is the side of the centred square whose nir / pred means are the last two columns
+    (0: NaN); it must fit into the window."""
+    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
+        raise ValueError(f"nir/pred must be equal-shaped [B, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
+    B, _, H, W = nir.shape
+    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
+        raise ValueError(f"rgb must be [B, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
+    if pred.device != nir.device or (rgb is not None and rgb.device != nir.device) or (nir.device.type != "cuda" and not L.is_emulated()):
+        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
+    n = nir.detach().to(torch.float32).contiguous()
+    p = pred.detach().to(torch.float32).contiguous()
+    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    ch, cw = (H, W) if crop is None else (int(crop), int(crop))
+    be = L.backend()
+    ws = torch.empty(int(be.nirgan_tile_metrics_ws_elems(B, ch, cw)), dtype=torch.float32, device=n.device)
+    rows = torch.full((B, L.TILE_METRIC_COLS), float("nan"), dtype=torch.float32, device=n.device)
+    d = L.TileMetricsDesc()
+    d.rgb = None if c is None else c.data_ptr()
+    d.nir, d.pred, d.B, d.H, d.W = n.data_ptr(), p.data_ptr(), B, H, W
+    d.y0, d.x0, d.ch, d.cw = (H - ch) // 2, (W - cw) // 2, ch, cw
+    d.window, d.sigma, d.max_val, d.eps, d.patch = int(window_size), float(sigma), float(max_val), float(eps), int(patch)
+    d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
+    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
+    L.check(be.nirgan_tile_metrics(C.byref(d), st), "tile_metrics")
+    return rows
