@@ -509,6 +509,31 @@ int64_t nirgan_tile_metrics_ws_elems(int B, int ch, int cw);
 int nirgan_tile_metrics(const nirgan_tile_metrics_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Window statistics of a date stack: the numbers of the reference's NDVI time series (validation_utils/time_series_validation.py:
+ * centroid patch means :120-132, window medians of the NDVI :243-266; per date on CPU copies there), ONE launch for the whole stack.
+ * Per tile t, over the window [y0, y0+wh) x [x0, x0+ww) of the stored images:
+ *   rows[t][0], rows[t][1]   mean, median of nir              rows[t][2], rows[t][3]   mean, median of pred
+ *   rows[t][4], rows[t][5]   mean, median of ndvi(nir)        rows[t][6], rows[t][7]   mean, median of ndvi(pred)
+ * with ndvi(n) = (n - R) / ((n + R) + 1e-6f), R = rgb[t][0] (the association of the pixel-loss entry above).  rgb == NULL: columns
+ * 4 to 7 stay untouched.  Every computed column is OVERWRITTEN.
+ * Median = torch.median of the flattened window: one of the window's values (exact radix selection on the device, no interpolation),
+ * the LOWER of the two middle values of an even count, NaN with a NaN anywhere in the window; the sign of a zero is unspecified.
+ * Means are fixed-order partial sums whose association depends only on (wh, ww): a tile's row is bitwise the same alone and inside
+ * any stack, and two calls are bitwise equal (no float atomics).  Any T, H, W >= 1 and any window inside the image; no workspace.
+ * Argument errors (null nir, pred or rows, window outside the image, non-positive extent) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_WINDOW_STAT_COLS 8   /* mean_nir, median_nir, mean_pred, median_pred, mean_ndvi_nir, median_ndvi_nir, mean_ndvi_pred, median_ndvi_pred */
+typedef struct {
+    const float* rgb;          /* [T][3][H][W] fp32 NCHW, may be NULL: the NDVI columns are then not computed */
+    const float* nir;          /* [T][1][H][W] */
+    const float* pred;         /* [T][1][H][W] */
+    int T, H, W;
+    int y0, x0, wh, ww;        /* the window inside each image */
+    float* rows;               /* [T][NIRGAN_WINDOW_STAT_COLS] on device, OVERWRITTEN */
+} nirgan_window_stats_desc;
+int nirgan_window_stats(const nirgan_window_stats_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * SSIM term of the generator objective, value AND gradient: model/pix2pix.py:233-237 adds
  * lambda_ssim * ssim_loss(pred, nir); utils/losses.py:10-30: 1 - kornia.metrics.ssim(img1, img2, window_size=11).mean()
  * (Gaussian window sigma 1.5, reflect border, max_val 1, eps 1e-12 in the denominator).

@@ -10,7 +10,9 @@ reference's keys (train.py:61-65 / create_synthetic_dataset.py:24-26 load it wit
 callbacks are out of scope.  Data parallel: pass a ``parallel.GradReducer`` (one process per GPU, RCCL); validation
 metrics are averaged over ranks when a process group is initialised.  ``tile_table_path``: every validation epoch also
 writes the per-tile metrics table of its validation batches (validation_utils.tile_metrics.evaluate_tiles, the reference's
-spider_validation_callback) to ``<stem>_e<epoch><ext>``; rank 0 writes it under data parallel.
+spider_validation_callback) to ``<stem>_e<epoch><ext>``; rank 0 writes it under data parallel.  ``time_series``: every
+``time_series_every`` validation epochs the NDVI time series of a date stack (validation_utils.time_series_validation.ndvi_timeline,
+what the reference plots from on_validation_epoch_end, model/pix2pix.py:347-412) is appended to ``history["time_series"]``.
 """
 from __future__ import annotations
 
@@ -39,15 +41,28 @@ def _write_tile_table(model, val_loader, device, path, crop, epoch):
     evaluate_tiles(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
 
 
+def _time_series(model, time_series, device, epoch):
+    """ndvi_timeline of the stack under the model as it is now: ``time_series`` is a glob of rasters or a (rgbs, nirs) pair"""
+    from validation_utils.time_series_validation import get_pred_nirs_and_info, ndvi_timeline, predict_stack
+    if isinstance(time_series, str):
+        rgbs, nirs, preds, _ = get_pred_nirs_and_info(model, device, time_series)
+    else:
+        rgbs, nirs = (torch.as_tensor(t).to(device) for t in time_series)
+        preds = predict_stack(model, rgbs)
+    return {"epoch": epoch, **ndvi_timeline(rgbs, nirs, preds)}
+
+
 def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                  tile_table_path=None, tile_table_crop=240):
+                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1):
     """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
     (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
     if reducer is not None:
         raise NotImplementedError("data-parallel training of the baseline models is not on the MI355X path")
     optim = model.configure_optimizers()
     history = {"train": [], "val": [], "lr": []}
-    step, first_epoch = 0, 0
+    if time_series is not None:
+        history["time_series"] = []
+    step, first_epoch, val_epochs = 0, 0, 0
     if resume_from is not None:
         ck = torch.load(resume_from, map_location=device, weights_only=False)
         model.load_state_dict(ck["state_dict"], strict=True)
@@ -83,6 +98,9 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
                 on_log(val)
             if tile_table_path is not None:
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
+            if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
+                history["time_series"].append(_time_series(model, time_series, device, epoch))
+            val_epochs += 1
         history["lr"].append({"epoch": epoch, "lr": model.lr})
         if ckpt_path is not None:
             torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(),
@@ -93,20 +111,25 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
 def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]] = None, *, max_epochs: int = 1,
         device=None, reducer=None, log_every: int = 10, on_log: Optional[Callable[[Dict[str, float]], None]] = None,
         ckpt_path: Optional[str] = None, resume_from: Optional[str] = None, tile_table_path: Optional[str] = None,
-        tile_table_crop: Optional[int] = 240) -> Dict[str, list]:
+        tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1) -> Dict[str, list]:
     """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
     {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
-    per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles)."""
+    per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles).
+    ``time_series`` (default None: nothing changes): a glob of date rasters (validation_utils.get_pred_nirs_and_info) or a
+    ``(rgbs [T,3,H,W], nirs [T,1,H,W])`` pair; every ``time_series_every`` validation epochs ``ndvi_timeline``'s dict of the stack
+    under the current model (plus ``epoch``) is appended to ``history["time_series"]``."""
     device = device or next(model.parameters()).device
     if getattr(model, "is_pixel_baseline", False):
         return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                             tile_table_path, tile_table_crop)
+                             tile_table_path, tile_table_crop, time_series, time_series_every)
     trainer = model.fused_trainer(reducer=reducer)
     (optim_d, optim_g), scheds = model.configure_optimizers()
     sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
     monitor = scheds[0]["monitor"]
     history = {"train": [], "val": [], "lr": []}
-    step, first_epoch = 0, 0
+    if time_series is not None:
+        history["time_series"] = []
+    step, first_epoch, val_epochs = 0, 0, 0
     if resume_from is not None:
         ck = torch.load(resume_from, map_location=device, weights_only=False)
         model.load_state_dict(ck["state_dict"], strict=False)
@@ -150,6 +173,9 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
                 trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
             if tile_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
+            if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
+                history["time_series"].append(_time_series(model, time_series, device, epoch))
+            val_epochs += 1
         history["lr"].append({"epoch": epoch, "lr_d": trainer.lr if trainer.lr_d is None else trainer.lr_d,
                               "lr_g": trainer.lr if trainer.lr_g is None else trainer.lr_g})
         if ckpt_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):

@@ -128,6 +128,14 @@ class TileMetricsDesc(C.Structure):
                 ("ws", fp), ("ws_elems", i64), ("rows", fp)]
 
 
+WINDOW_STAT_COLS = 8            # include/nirgan_hip.h: NIRGAN_WINDOW_STAT_COLS
+
+
+class WindowStatsDesc(C.Structure):
+    _fields_ = [("rgb", fp), ("nir", fp), ("pred", fp), ("T", i32), ("H", i32), ("W", i32),
+                ("y0", i32), ("x0", i32), ("wh", i32), ("ww", i32), ("rows", fp)]
+
+
 class SsimLossDesc(C.Structure):
     _fields_ = [("pred", fp), ("target", fp), ("planes", i32), ("H", i32), ("W", i32), ("window", i32), ("sigma", f32), ("max_val", f32),
                 ("eps", f32), ("weight", f32), ("ws", fp), ("ws_elems", i64), ("loss", fp), ("value", fp), ("grad_pred", fp)]
@@ -224,6 +232,7 @@ PROTOTYPES = {
     "nirgan_image_metrics": (i32, [C.POINTER(MetricsDesc), fp]),
     "nirgan_tile_metrics_ws_elems": (i64, [i32, i32, i32]),
     "nirgan_tile_metrics": (i32, [C.POINTER(TileMetricsDesc), fp]),
+    "nirgan_window_stats": (i32, [C.POINTER(WindowStatsDesc), fp]),
     "nirgan_ssim_loss_ws_elems": (i64, [i32, i32, i32, i32]),
     "nirgan_ssim_loss": (i32, [C.POINTER(SsimLossDesc), fp]),
     "nirgan_emd_loss_ws_bytes": (i64, [i32, i64, i32]),

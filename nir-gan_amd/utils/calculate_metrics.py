@@ -10,6 +10,9 @@ tensor without synchronising, for callers that log asynchronously.
 ``tile_metrics_device(rgb, nir, pred, crop, ..)`` is the per-tile form behind the validation table
 (validation_utils/): one row of ``TILE_METRIC_COLUMNS`` per tile of the batch in ONE fused pass (nirgan_tile_metrics),
 the centre crop applied by indexing.
+
+``window_stats_device(rgb, nir, pred, y0, x0, wh, ww)`` gives the mean and the median of nir, pred and their NDVI over one window
+of every tile of a date stack (nirgan_window_stats): the numbers behind validation_utils/time_series_validation.py.
 """
 import ctypes as C
 import math
@@ -91,4 +94,36 @@ def tile_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, w
     d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
     st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
     L.check(be.nirgan_tile_metrics(C.byref(d), st), "tile_metrics")
+    return rows
+
+
+# column order of nirgan_window_stats rows (include/nirgan_hip.h)
+WINDOW_STAT_COLUMNS = ("mean_nir", "median_nir", "mean_pred", "median_pred",
+                       "mean_ndvi_nir", "median_ndvi_nir", "mean_ndvi_pred", "median_ndvi_pred")
+assert len(WINDOW_STAT_COLUMNS) == L.WINDOW_STAT_COLS
+
+
+def window_stats_device(rgb, nir: torch.Tensor, pred: torch.Tensor, y0: int, x0: int, wh: int, ww: int) -> torch.Tensor:
+    """One row of ``WINDOW_STAT_COLUMNS`` per tile: a ``T x 8`` fp32 tensor on the inputs' device, no host sync.
+
+    ``nir`` / ``pred`` are [T, 1, H, W], ``rgb`` [T, 3, H, W] (more bands are cut to the first three) or ``None``: the four NDVI
+    columns are then NaN.  The window is rows ``y0 .. y0 + wh``, columns ``x0 .. x0 + ww`` of every tile, applied by indexing.
+    The medians are ``torch.median`` of the flattened window (the lower middle value of an even count, NaN with any NaN)."""
+    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
+        raise ValueError(f"nir/pred must be equal-shaped [T, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
+    T, _, H, W = nir.shape
+    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != T or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
+        raise ValueError(f"rgb must be [T, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
+    if pred.device != nir.device or (rgb is not None and rgb.device != nir.device) or (nir.device.type != "cuda" and not L.is_emulated()):
+        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
+    n = nir.detach().to(torch.float32).contiguous()
+    p = pred.detach().to(torch.float32).contiguous()
+    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    rows = torch.full((T, L.WINDOW_STAT_COLS), float("nan"), dtype=torch.float32, device=n.device)
+    d = L.WindowStatsDesc()
+    d.rgb = None if c is None else c.data_ptr()
+    d.nir, d.pred, d.T, d.H, d.W = n.data_ptr(), p.data_ptr(), T, H, W
+    d.y0, d.x0, d.wh, d.ww, d.rows = int(y0), int(x0), int(wh), int(ww), rows.data_ptr()
+    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
+    L.check(L.backend().nirgan_window_stats(C.byref(d), st), "window_stats")
     return rows

@@ -1,5 +1,8 @@
 """MI355X-native counterpart of the reference's ``validation_utils`` package: the per-tile metrics table
-(get_results_table.py:59-94, spider_validation_callback.py:28-64) built on one fused device pass per batch.
-The geo-context join (geopandas), the PNG plots and the time-series plots are out of scope."""
+(get_results_table.py:59-94, spider_validation_callback.py:28-64) built on one fused device pass per batch, and the NDVI time
+series (time_series_validation.py) on batched predictions and one device call per window.
+The geo-context join (geopandas) and the table's PNG plots are out of scope."""
 from .tile_metrics import TABLE_KEYS, evaluate_tiles, spider_validation_callback  # noqa: F401
+from .time_series_validation import (calculate_and_plot_timeline, get_pred_nirs_and_info, ndvi_timeline,  # noqa: F401
+                                     plot_ndvi_timeline, plot_timeline)
 from .val_utils import crop_center  # noqa: F401
