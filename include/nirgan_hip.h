@@ -534,6 +534,57 @@ typedef struct {
 int nirgan_window_stats(const nirgan_window_stats_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Validation figure panels: the numbers and display planes behind the reference's two validation figures (utils/logging_helpers.py:
+ * plot_tensors_hist :68-136, plot_index :139-193) and the per-tile parts of its val_stats scalars (model/pix2pix.py:301-309); per image on CPU
+ * copies there, ONE entry call for a whole batch here.  Per tile b, with v(x) = clamp(gain * x, 0, 1) in fp32 and the window
+ * [y0, y0+ch) x [x0, x0+cw) of the stored images:
+ *   hist[b][0][100], hist[b][1][100]   counts of v(nir), v(pred) over the window: bit-exactly np.histogram(v, bins=100, range=(0, 1))[0] on
+ *                      float32 input, i.e. the edges are np.linspace(0, 1, 101, dtype=float32), a value goes to the bin i with
+ *                      edge[i] <= v < edge[i+1], the last bin is closed at 1 and a NaN is counted nowhere
+ *   stats[b][0..2]     min, max, mean of raw nir over the FULL tile;   stats[b][3..5] the same of raw pred
+ *   stats[b][6..7]     rgb_lo, rgb_hi: the perc-th and the (100 - perc)-th percentile of all 3*H*W values of the tile's rgb (clamped to
+ *                      [0, 1] first when clamp_rgb = 1, raw when 0), as torch.quantile(x.flatten(), q) with linear interpolation:
+ *                      pos = q (n - 1) in double on the host, a + t (b - a) on the order statistics of rank floor(pos) and ceil(pos)
+ *                      (taken from b's end for t >= 0.5, as torch's lerp), evaluated in double and rounded once.  The order statistics are EXACT (radix selection on the sign-corrected bit
+ *                      pattern: no sort, no sampling).  rgb == NULL: these two stay untouched
+ *   nir_disp, pred_disp [b][ch][cw]             v(nir), v(pred) over the window
+ *   ndvi_nir_disp, ndvi_pred_disp [b][ch][cw]   (clip(ndvi(n), -1, 1) + 1) / 2 with ndvi(n) = (n - R) / ((n + R) + 1e-6f) from RAW values,
+ *                      R = rgb[b][0] (the association and IEEE division of the pixel-loss entry above)
+ *   rgb_disp [b][ch][cw][3] (channel last)      clamp((c - rgb_lo) / (rgb_hi - rgb_lo), 0, 1), c clamped to [0, 1] first when clamp_rgb = 1;
+ *                      0 where rgb_hi == rgb_lo
+ * The reference's minmax_percentile lives in data/normalise_s2.py, which it does not ship: the percentile stretch above is THIS project's
+ * reading of it.  It is per image, so a tile's output does not depend on its batch neighbours.
+ * A NaN anywhere in a tile's nir, pred or rgb gives NaN in that tile's affected columns only (torch.min / max / mean / quantile).
+ * Every output pointer may be NULL: that output is not computed.  Every computed output is OVERWRITTEN.  ws: at least _ws_bytes bytes.
+ * Deterministic: means are fixed-order partial sums whose association depends only on (H, W), counts are integer atomics (they commute),
+ * no float atomics: a tile's every output is bitwise the same alone and inside any batch, and two calls are bitwise equal.
+ * Argument errors (null nir or pred, a non-positive extent, a window outside the image, perc outside [0, 50), ndvi_*_disp or rgb_disp without
+ * rgb, workspace too small, B*3*H*W >= 2^31) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_PANEL_BINS 100
+#define NIRGAN_PANEL_STAT_COLS 8    /* min_nir, max_nir, mean_nir, min_pred, max_pred, mean_pred, rgb_lo, rgb_hi */
+typedef struct {
+    const float* rgb;          /* [B][3][H][W] fp32 NCHW, may be NULL */
+    const float* nir;          /* [B][1][H][W] */
+    const float* pred;         /* [B][1][H][W] */
+    int B, H, W;
+    int y0, x0, ch, cw;        /* the window inside each image */
+    float gain;                /* stretch of nir and pred before the histogram and the display (the reference's figure: 1.5f) */
+    float perc;                /* percentile of the rgb stretch, in [0, 50) (the reference: 2) */
+    int clamp_rgb;             /* 1: rgb is clamped to [0, 1] before the percentiles and the stretch (plot_tensors_hist); 0: raw (plot_index) */
+    void* ws; int64_t ws_bytes;
+    int32_t* hist;             /* [B][2][NIRGAN_PANEL_BINS] */
+    float* stats;              /* [B][NIRGAN_PANEL_STAT_COLS] */
+    float* nir_disp;           /* [B][ch][cw] */
+    float* pred_disp;          /* [B][ch][cw] */
+    float* ndvi_nir_disp;      /* [B][ch][cw], needs rgb */
+    float* ndvi_pred_disp;     /* [B][ch][cw], needs rgb */
+    float* rgb_disp;           /* [B][ch][cw][3], needs rgb */
+} nirgan_val_panel_desc;
+int64_t nirgan_val_panel_ws_bytes(int B, int H, int W);
+int nirgan_val_panel(const nirgan_val_panel_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * SSIM term of the generator objective, value AND gradient: model/pix2pix.py:233-237 adds
  * lambda_ssim * ssim_loss(pred, nir); utils/losses.py:10-30: 1 - kornia.metrics.ssim(img1, img2, window_size=11).mean()
  * (Gaussian window sigma 1.5, reflect border, max_val 1, eps 1e-12 in the denominator).

@@ -96,6 +96,15 @@ class _PixelBaseline(_Base):
             self._log(k, v)
         return metrics["val/L1"]
 
+    @torch.no_grad()
+    def validation_figures(self, batch) -> dict:
+        """The figures the reference logs from validation_step (baseline_models.py:43-55): ``Images/Val NIR`` and, with
+        ``custom_configs.Logging.log_ndvi``, ``Images/Val NDVI``, as images (utils.logging_helpers); wandb stays out."""
+        assert self.training == False, "Model is in training mode, set to eval mode before plotting validation figures"
+        from utils.logging_helpers import validation_figures
+        rgb, nir = batch["rgb"], batch["nir"]
+        return validation_figures(self, rgb[:, :3], nir, self(rgb))
+
     def configure_optimizers(self):
         return HipAdam(self.parameters(), lr=self.lr, net=self)
 

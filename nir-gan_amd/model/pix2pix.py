@@ -199,6 +199,21 @@ class Px2Px_PL(_Base):
                     self._log(k, v)
         return metrics["val/L1"]
 
+    @torch.no_grad()
+    def validation_figures(self, batch) -> dict:
+        """The figures the reference logs from validation_step (pix2pix.py:286-298): ``Images/Val NIR`` (plot_tensors_hist) and, with
+        ``custom_configs.Logging.log_ndvi``, ``Images/Val NDVI`` (plot_index), as images; the prediction is validation_step's.  The
+        numbers behind each figure come from one nirgan_val_panel call (utils.logging_helpers).  wandb stays out."""
+        assert self.training == False, "Model is in training mode, set to eval mode before plotting validation figures"
+        from utils.logging_helpers import validation_figures
+        embeds = None
+        if self.satclip == False:
+            rgb, nir = self.extract_batch(batch)
+        else:
+            rgb, nir, embeds = self.extract_batch(batch)
+        nir_pred = self.predict_step(rgb, embeds) if embeds is not None else self.predict_step(rgb)
+        return validation_figures(self, rgb[:, :3, :, :], nir, nir_pred)
+
     def _wants_metrics(self) -> bool:
         """The reference logs only when a logger with an experiment is attached (pix2pix.py:182, :280); without
         Lightning the values go to ``self.logged``."""

@@ -6,13 +6,15 @@ path: per batch the two optimizer passes (here ONE fused call, ``model.train_bat
 for both optimizers (model/pix2pix.py:485-492), plus a checkpoint in Lightning's layout: ``state_dict`` with the
 reference's keys (train.py:61-65 / create_synthetic_dataset.py:24-26 load it with ``strict=False``), ``optimizer_states``
 (both Adams: moments and step counts, torch.optim.Adam's format) and ``lr_schedulers`` (both ReduceLROnPlateau), so that
-``resume_from`` continues a run the way ``Trainer(resume_from_checkpoint=...)`` does (train.py:66-70,126).  Loggers, wandb, image plots and
+``resume_from`` continues a run the way ``Trainer(resume_from_checkpoint=...)`` does (train.py:66-70,126).  Loggers, wandb and
 callbacks are out of scope.  Data parallel: pass a ``parallel.GradReducer`` (one process per GPU, RCCL); validation
 metrics are averaged over ranks when a process group is initialised.  ``tile_table_path``: every validation epoch also
 writes the per-tile metrics table of its validation batches (validation_utils.tile_metrics.evaluate_tiles, the reference's
 spider_validation_callback) to ``<stem>_e<epoch><ext>``; rank 0 writes it under data parallel.  ``time_series``: every
 ``time_series_every`` validation epochs the NDVI time series of a date stack (validation_utils.time_series_validation.ndvi_timeline,
-what the reference plots from on_validation_epoch_end, model/pix2pix.py:347-412) is appended to ``history["time_series"]``.
+what the reference plots from on_validation_epoch_end, model/pix2pix.py:347-412) is appended to ``history["time_series"]``.  ``figures_dir``: every ``figures_every`` validation epochs the reference's two validation figures
+(utils.logging_helpers, model/pix2pix.py:286-298) of the first ``Logging.num_val_images`` validation batches are written as PNG files.
+wandb and Lightning loggers stay out of scope.
 """
 from __future__ import annotations
 
@@ -52,8 +54,28 @@ def _time_series(model, time_series, device, epoch):
     return {"epoch": epoch, **ndvi_timeline(rgbs, nirs, preds)}
 
 
+def _write_figures(model, val_loader, device, figures_dir, epoch, history):
+    """val_nir_e<epoch>_b<i>.png (and val_ndvi_.. with Logging.log_ndvi) of the first Logging.num_val_images validation batches"""
+    import os
+    from model.pix2pix import _cfg
+    count = int(_cfg(_cfg(_cfg(model.config, "custom_configs"), "Logging"), "num_val_images", 0) or 0)
+    os.makedirs(figures_dir, exist_ok=True)
+    names = {"Images/Val NIR": "val_nir", "Images/Val NDVI": "val_ndvi"}
+    for i, batch in enumerate(val_loader):
+        if i >= count:
+            break
+        for key, im in model.validation_figures(_to_device(batch, device)).items():
+            path = os.path.join(figures_dir, f"{names[key]}_e{epoch}_b{i}.png")
+            if hasattr(im, "save"):
+                im.save(path)
+            else:                                            # without Pillow the helper returns an H x W x 4 array
+                import matplotlib.image
+                matplotlib.image.imsave(path, im)
+            history["figures"].append(path)
+
+
 def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1):
+                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1, figures_dir=None, figures_every=1):
     """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
     (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
     if reducer is not None:
@@ -62,6 +84,8 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
     history = {"train": [], "val": [], "lr": []}
     if time_series is not None:
         history["time_series"] = []
+    if figures_dir is not None:
+        history["figures"] = []
     step, first_epoch, val_epochs = 0, 0, 0
     if resume_from is not None:
         ck = torch.load(resume_from, map_location=device, weights_only=False)
@@ -100,6 +124,8 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
             if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
                 history["time_series"].append(_time_series(model, time_series, device, epoch))
+            if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0:
+                _write_figures(model, val_loader, device, figures_dir, epoch, history)
             val_epochs += 1
         history["lr"].append({"epoch": epoch, "lr": model.lr})
         if ckpt_path is not None:
@@ -111,17 +137,21 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
 def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]] = None, *, max_epochs: int = 1,
         device=None, reducer=None, log_every: int = 10, on_log: Optional[Callable[[Dict[str, float]], None]] = None,
         ckpt_path: Optional[str] = None, resume_from: Optional[str] = None, tile_table_path: Optional[str] = None,
-        tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1) -> Dict[str, list]:
+        tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1,
+        figures_dir: Optional[str] = None, figures_every: int = 1) -> Dict[str, list]:
     """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
     {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
     per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles).
     ``time_series`` (default None: nothing changes): a glob of date rasters (validation_utils.get_pred_nirs_and_info) or a
     ``(rgbs [T,3,H,W], nirs [T,1,H,W])`` pair; every ``time_series_every`` validation epochs ``ndvi_timeline``'s dict of the stack
-    under the current model (plus ``epoch``) is appended to ``history["time_series"]``."""
+    under the current model (plus ``epoch``) is appended to ``history["time_series"]``.  ``figures_dir`` (default None: nothing
+    changes): every ``figures_every`` validation epochs the validation figures (``model.validation_figures``) of the first
+    ``Logging.num_val_images`` validation batches are written there as ``val_nir_e<epoch>_b<i>.png`` / ``val_ndvi_e<epoch>_b<i>.png``
+    (rank 0 under data parallel) and the paths appended to ``history["figures"]``."""
     device = device or next(model.parameters()).device
     if getattr(model, "is_pixel_baseline", False):
         return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                             tile_table_path, tile_table_crop, time_series, time_series_every)
+                             tile_table_path, tile_table_crop, time_series, time_series_every, figures_dir, figures_every)
     trainer = model.fused_trainer(reducer=reducer)
     (optim_d, optim_g), scheds = model.configure_optimizers()
     sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
@@ -129,6 +159,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
     history = {"train": [], "val": [], "lr": []}
     if time_series is not None:
         history["time_series"] = []
+    if figures_dir is not None:
+        history["figures"] = []
     step, first_epoch, val_epochs = 0, 0, 0
     if resume_from is not None:
         ck = torch.load(resume_from, map_location=device, weights_only=False)
@@ -175,6 +207,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
             if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
                 history["time_series"].append(_time_series(model, time_series, device, epoch))
+            if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0 and (reducer is None or getattr(reducer, "rank", 0) == 0):
+                _write_figures(model, val_loader, device, figures_dir, epoch, history)
             val_epochs += 1
         history["lr"].append({"epoch": epoch, "lr_d": trainer.lr if trainer.lr_d is None else trainer.lr_d,
                               "lr_g": trainer.lr if trainer.lr_g is None else trainer.lr_g})

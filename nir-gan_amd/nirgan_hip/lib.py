@@ -136,6 +136,17 @@ class WindowStatsDesc(C.Structure):
                 ("y0", i32), ("x0", i32), ("wh", i32), ("ww", i32), ("rows", fp)]
 
 
+PANEL_BINS = 100                # include/nirgan_hip.h: NIRGAN_PANEL_BINS
+PANEL_STAT_COLS = 8             # include/nirgan_hip.h: NIRGAN_PANEL_STAT_COLS
+
+
+class ValPanelDesc(C.Structure):
+    _fields_ = [("rgb", fp), ("nir", fp), ("pred", fp), ("B", i32), ("H", i32), ("W", i32),
+                ("y0", i32), ("x0", i32), ("ch", i32), ("cw", i32), ("gain", f32), ("perc", f32), ("clamp_rgb", i32),
+                ("ws", fp), ("ws_bytes", i64), ("hist", fp), ("stats", fp), ("nir_disp", fp), ("pred_disp", fp),
+                ("ndvi_nir_disp", fp), ("ndvi_pred_disp", fp), ("rgb_disp", fp)]
+
+
 class SsimLossDesc(C.Structure):
     _fields_ = [("pred", fp), ("target", fp), ("planes", i32), ("H", i32), ("W", i32), ("window", i32), ("sigma", f32), ("max_val", f32),
                 ("eps", f32), ("weight", f32), ("ws", fp), ("ws_elems", i64), ("loss", fp), ("value", fp), ("grad_pred", fp)]
@@ -233,6 +244,8 @@ PROTOTYPES = {
     "nirgan_tile_metrics_ws_elems": (i64, [i32, i32, i32]),
     "nirgan_tile_metrics": (i32, [C.POINTER(TileMetricsDesc), fp]),
     "nirgan_window_stats": (i32, [C.POINTER(WindowStatsDesc), fp]),
+    "nirgan_val_panel_ws_bytes": (i64, [i32, i32, i32]),
+    "nirgan_val_panel": (i32, [C.POINTER(ValPanelDesc), fp]),
     "nirgan_ssim_loss_ws_elems": (i64, [i32, i32, i32, i32]),
     "nirgan_ssim_loss": (i32, [C.POINTER(SsimLossDesc), fp]),
     "nirgan_emd_loss_ws_bytes": (i64, [i32, i64, i32]),
