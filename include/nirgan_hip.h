@@ -585,6 +585,40 @@ int64_t nirgan_val_panel_ws_bytes(int B, int H, int W);
 int nirgan_val_panel(const nirgan_val_panel_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Land-cover-stratified validation metrics: the per-tile rows above split by the class id of a mask (the five-class CLC legend of the
+ * reference's utils/plot_clc_utils.py / utils/plot_clc_pred.py: 0 none, 1 agricultural, 2 natural vegetation, 3 water, 4 artificial),
+ * ONE device pass for a whole batch.  Per tile b and class c < classes, over the pixels of the evaluation window
+ * [y0, y0+ch) x [x0, x0+cw) whose mask value equals c:
+ *   rows[b][c][0] count  = their number, exact (ch * cw < 2^24), stored as a float
+ *   rows[b][c][1] l1     = mean |nir - pred|                  rows[b][c][2] l2 = mean (nir - pred)^2
+ *   rows[b][c][3] ssim   = mean over those pixels of the SSIM map of the WHOLE window: the Gaussian filter crosses class borders and
+ *                          reflects at the window's border, exactly as in the per-tile entry
+ *   rows[b][c][4] psnr   = 10 log10(max_val^2 / l2), +inf where l2 == 0
+ *   rows[b][c][5..7]     = mean |idx(pred) - idx(nir)| for NDVI, NDWI, EVI, formulas and epsilons of the per-tile entry.
+ *                          rgb == NULL: these three stay untouched
+ * count == 0: every other computed column of that row is NaN.  Mask ids >= classes belong to no class.  No pixel outside the window is
+ * read, of the images or of the mask.  Every computed column is OVERWRITTEN.  ws: at least the _ws_elems count of floats.
+ * Deterministic: counts are added as integers, the float partial sums in a fixed order that depends only on (ch, cw, classes), so a
+ * tile's rows are bitwise the same alone and inside any batch and two calls are bitwise equal (no float atomics).
+ * Argument errors (everything the per-tile entry rejects, a null mask, classes outside 1..NIRGAN_CLASS_MAX, ch * cw >= 2^24, workspace
+ * too small) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_CLASS_MAX 8
+#define NIRGAN_CLASS_METRIC_COLS 8   /* count, l1, l2, ssim, psnr, l1_ndvi, l1_ndwi, l1_evi */
+typedef struct {
+    const float* rgb;            /* [B][3][H][W], may be NULL: index columns untouched */
+    const float* nir; const float* pred;   /* [B][1][H][W] */
+    const uint8_t* mask;         /* [B][H][W] class ids */
+    int B, H, W; int y0, x0, ch, cw;
+    int window; float sigma, max_val, eps; /* as nirgan_tile_metrics_desc */
+    int classes;                 /* 1..NIRGAN_CLASS_MAX */
+    float* ws; int64_t ws_elems;
+    float* rows;                 /* [B][classes][NIRGAN_CLASS_METRIC_COLS], OVERWRITTEN */
+} nirgan_class_metrics_desc;
+int64_t nirgan_class_metrics_ws_elems(int B, int ch, int cw, int classes);
+int nirgan_class_metrics(const nirgan_class_metrics_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * SSIM term of the generator objective, value AND gradient: model/pix2pix.py:233-237 adds
  * lambda_ssim * ssim_loss(pred, nir); utils/losses.py:10-30: 1 - kornia.metrics.ssim(img1, img2, window_size=11).mean()
  * (Gaussian window sigma 1.5, reflect border, max_val 1, eps 1e-12 in the denominator).

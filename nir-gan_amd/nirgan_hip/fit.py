@@ -14,6 +14,8 @@ spider_validation_callback) to ``<stem>_e<epoch><ext>``; rank 0 writes it under 
 ``time_series_every`` validation epochs the NDVI time series of a date stack (validation_utils.time_series_validation.ndvi_timeline,
 what the reference plots from on_validation_epoch_end, model/pix2pix.py:347-412) is appended to ``history["time_series"]``.  ``figures_dir``: every ``figures_every`` validation epochs the reference's two validation figures
 (utils.logging_helpers, model/pix2pix.py:286-298) of the first ``Logging.num_val_images`` validation batches are written as PNG files.
+``land_cover_table_path``: every validation epoch also writes the land-cover-stratified table (validation_utils.land_cover.
+evaluate_land_cover) of its validation batches to ``<stem>_e<epoch><ext>``, rank 0 under data parallel.
 wandb and Lightning loggers stay out of scope.
 """
 from __future__ import annotations
@@ -41,6 +43,13 @@ def _write_tile_table(model, val_loader, device, path, crop, epoch):
     from validation_utils.tile_metrics import evaluate_tiles
     stem, ext = os.path.splitext(path)
     evaluate_tiles(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
+
+
+def _write_land_cover_table(model, val_loader, device, path, crop, epoch):
+    import os
+    from validation_utils.land_cover import evaluate_land_cover
+    stem, ext = os.path.splitext(path)
+    evaluate_land_cover(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
 
 
 def _time_series(model, time_series, device, epoch):
@@ -75,7 +84,8 @@ def _write_figures(model, val_loader, device, figures_dir, epoch, history):
 
 
 def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1, figures_dir=None, figures_every=1):
+                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1, figures_dir=None, figures_every=1,
+                  land_cover_table_path=None, land_cover_crop=240):
     """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
     (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
     if reducer is not None:
@@ -122,6 +132,8 @@ def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, 
                 on_log(val)
             if tile_table_path is not None:
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
+            if land_cover_table_path is not None:
+                _write_land_cover_table(model, val_loader, device, land_cover_table_path, land_cover_crop, epoch)
             if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
                 history["time_series"].append(_time_series(model, time_series, device, epoch))
             if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0:
@@ -138,7 +150,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
         device=None, reducer=None, log_every: int = 10, on_log: Optional[Callable[[Dict[str, float]], None]] = None,
         ckpt_path: Optional[str] = None, resume_from: Optional[str] = None, tile_table_path: Optional[str] = None,
         tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1,
-        figures_dir: Optional[str] = None, figures_every: int = 1) -> Dict[str, list]:
+        figures_dir: Optional[str] = None, figures_every: int = 1, land_cover_table_path: Optional[str] = None,
+        land_cover_crop: Optional[int] = 240) -> Dict[str, list]:
     """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
     {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
     per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles).
@@ -147,11 +160,15 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
     under the current model (plus ``epoch``) is appended to ``history["time_series"]``.  ``figures_dir`` (default None: nothing
     changes): every ``figures_every`` validation epochs the validation figures (``model.validation_figures``) of the first
     ``Logging.num_val_images`` validation batches are written there as ``val_nir_e<epoch>_b<i>.png`` / ``val_ndvi_e<epoch>_b<i>.png``
-    (rank 0 under data parallel) and the paths appended to ``history["figures"]``."""
+    (rank 0 under data parallel) and the paths appended to ``history["figures"]``.  ``land_cover_table_path`` (default None: nothing
+    changes): per validation epoch, the land-cover-stratified table (validation_utils.evaluate_land_cover) of the validation batches,
+    which must then carry a ``mask`` of class ids, on the centred ``land_cover_crop`` window as ``<stem>_e<epoch><ext>`` (rank 0 under
+    data parallel)."""
     device = device or next(model.parameters()).device
     if getattr(model, "is_pixel_baseline", False):
         return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                             tile_table_path, tile_table_crop, time_series, time_series_every, figures_dir, figures_every)
+                             tile_table_path, tile_table_crop, time_series, time_series_every, figures_dir, figures_every,
+                             land_cover_table_path, land_cover_crop)
     trainer = model.fused_trainer(reducer=reducer)
     (optim_d, optim_g), scheds = model.configure_optimizers()
     sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
@@ -205,6 +222,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
                 trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
             if tile_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
                 _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
+            if land_cover_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
+                _write_land_cover_table(model, val_loader, device, land_cover_table_path, land_cover_crop, epoch)
             if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
                 history["time_series"].append(_time_series(model, time_series, device, epoch))
             if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0 and (reducer is None or getattr(reducer, "rank", 0) == 0):

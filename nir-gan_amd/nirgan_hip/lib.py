@@ -147,6 +147,17 @@ class ValPanelDesc(C.Structure):
                 ("ndvi_nir_disp", fp), ("ndvi_pred_disp", fp), ("rgb_disp", fp)]
 
 
+CLASS_MAX = 8                   # include/nirgan_hip.h: NIRGAN_CLASS_MAX
+CLASS_METRIC_COLS = 8           # include/nirgan_hip.h: NIRGAN_CLASS_METRIC_COLS
+
+
+class ClassMetricsDesc(C.Structure):
+    _fields_ = [("rgb", fp), ("nir", fp), ("pred", fp), ("mask", fp), ("B", i32), ("H", i32), ("W", i32),
+                ("y0", i32), ("x0", i32), ("ch", i32), ("cw", i32),
+                ("window", i32), ("sigma", f32), ("max_val", f32), ("eps", f32), ("classes", i32),
+                ("ws", fp), ("ws_elems", i64), ("rows", fp)]
+
+
 class SsimLossDesc(C.Structure):
     _fields_ = [("pred", fp), ("target", fp), ("planes", i32), ("H", i32), ("W", i32), ("window", i32), ("sigma", f32), ("max_val", f32),
                 ("eps", f32), ("weight", f32), ("ws", fp), ("ws_elems", i64), ("loss", fp), ("value", fp), ("grad_pred", fp)]
@@ -246,6 +257,8 @@ PROTOTYPES = {
     "nirgan_window_stats": (i32, [C.POINTER(WindowStatsDesc), fp]),
     "nirgan_val_panel_ws_bytes": (i64, [i32, i32, i32]),
     "nirgan_val_panel": (i32, [C.POINTER(ValPanelDesc), fp]),
+    "nirgan_class_metrics_ws_elems": (i64, [i32, i32, i32, i32]),
+    "nirgan_class_metrics": (i32, [C.POINTER(ClassMetricsDesc), fp]),
     "nirgan_ssim_loss_ws_elems": (i64, [i32, i32, i32, i32]),
     "nirgan_ssim_loss": (i32, [C.POINTER(SsimLossDesc), fp]),
     "nirgan_emd_loss_ws_bytes": (i64, [i32, i64, i32]),

@@ -13,6 +13,9 @@ the centre crop applied by indexing.
 
 ``window_stats_device(rgb, nir, pred, y0, x0, wh, ww)`` gives the mean and the median of nir, pred and their NDVI over one window
 of every tile of a date stack (nirgan_window_stats): the numbers behind validation_utils/time_series_validation.py.
+
+``class_metrics_device(rgb, nir, pred, mask, classes, crop, ..)`` splits the per-tile rows by the class id of a land-cover mask
+(nirgan_class_metrics): one row of ``CLASS_METRIC_COLUMNS`` per (tile, class) in ONE fused pass, behind validation_utils/land_cover.py.
 """
 import ctypes as C
 import math
@@ -126,4 +129,72 @@ def window_stats_device(rgb, nir: torch.Tensor, pred: torch.Tensor, y0: int, x0:
     d.y0, d.x0, d.wh, d.ww, d.rows = int(y0), int(x0), int(wh), int(ww), rows.data_ptr()
     st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
     L.check(L.backend().nirgan_window_stats(C.byref(d), st), "window_stats")
+    return rows
+
+
+# column order of nirgan_class_metrics rows (include/nirgan_hip.h)
+CLASS_METRIC_COLUMNS = ("count", "l1", "l2", "ssim", "psnr", "l1_ndvi", "l1_ndwi", "l1_evi")
+assert len(CLASS_METRIC_COLUMNS) == L.CLASS_METRIC_COLS
+
+
+def _mask_uint8(mask: torch.Tensor, y0: int, x0: int, ch: int, cw: int) -> torch.Tensor:
+    """[B, H, W] class ids of any integer or float dtype as uint8 on the same device.  Only the evaluation window is looked at (and
+    converted): ids there must be integral and lie in 0..255.  The check reads one flag back, so a uint8 mask skips it."""
+    if mask.dtype == torch.uint8:
+        return mask.contiguous()
+    if mask.dtype == torch.bool:
+        return mask.to(torch.uint8).contiguous()
+    B, H, W = mask.shape
+    out = torch.zeros((B, H, W), dtype=torch.uint8, device=mask.device)
+    if y0 < 0 or x0 < 0 or ch <= 0 or cw <= 0 or y0 + ch > H or x0 + cw > W:
+        return out                                          # a bad window is the entry's error to raise
+    w = mask[:, y0:y0 + ch, x0:x0 + cw]
+    bad = ~((w >= 0) & (w <= 255))                          # a NaN fails both comparisons
+    if w.is_floating_point():
+        bad |= w != w.floor()
+    if bool(bad.any()):
+        raise ValueError("mask values inside the evaluation window must be integral class ids in 0..255")
+    out[:, y0:y0 + ch, x0:x0 + cw] = w.to(torch.uint8)
+    return out
+
+
+def class_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, mask: torch.Tensor, classes: int = 5, crop=None,
+                         window_size: int = 11, max_val: float = 1.0, sigma: float = 1.5, eps: float = 1e-12) -> torch.Tensor:
+    """One row of ``CLASS_METRIC_COLUMNS`` per (tile, class): a ``B x classes x 8`` fp32 tensor on the inputs' device.
+
+    ``nir`` / ``pred`` are [B, 1, H, W], ``rgb`` [B, 3, H, W] (more bands are cut to the first three) or ``None``: the three index
+    columns are then NaN.  ``mask`` is [B, H, W] or [B, 1, H, W] class ids: uint8 goes to the device entry as it is (no host sync);
+    any other integer or float dtype (the reference hands its masks through ``torch.Tensor(..)``) is converted on the device after
+    a check that every id inside the evaluation window is integral and in 0..255 (``ValueError`` otherwise; the check reads one
+    flag back).  Ids ``>= classes`` belong to no class.  ``crop`` as in ``tile_metrics_device``: the SSIM map is that of the whole
+    window, each class takes the mean over its own pixels; a class without pixels has count 0 and NaN elsewhere."""
+    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
+        raise ValueError(f"nir/pred must be equal-shaped [B, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
+    B, _, H, W = nir.shape
+    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
+        raise ValueError(f"rgb must be [B, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
+    if not torch.is_tensor(mask) or tuple(mask.shape) not in ((B, H, W), (B, 1, H, W)) or mask.is_complex():
+        raise ValueError(f"mask must be a [B, H, W] or [B, 1, H, W] tensor of class ids matching nir, got {tuple(getattr(mask, 'shape', ()))}")
+    if not 1 <= int(classes) <= L.CLASS_MAX:
+        raise ValueError(f"classes must lie in 1..{L.CLASS_MAX}, got {classes}")
+    if (pred.device != nir.device or mask.device != nir.device or (rgb is not None and rgb.device != nir.device)
+            or (nir.device.type != "cuda" and not L.is_emulated())):
+        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
+    n = nir.detach().to(torch.float32).contiguous()
+    p = pred.detach().to(torch.float32).contiguous()
+    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    ch, cw = (H, W) if crop is None else (int(crop), int(crop))
+    y0, x0 = (H - ch) // 2, (W - cw) // 2
+    m = _mask_uint8(mask.detach().reshape(B, H, W), y0, x0, ch, cw)
+    be = L.backend()
+    ws = torch.empty(int(be.nirgan_class_metrics_ws_elems(B, ch, cw, int(classes))), dtype=torch.float32, device=n.device)
+    rows = torch.full((B, int(classes), L.CLASS_METRIC_COLS), float("nan"), dtype=torch.float32, device=n.device)
+    d = L.ClassMetricsDesc()
+    d.rgb = None if c is None else c.data_ptr()
+    d.nir, d.pred, d.mask, d.B, d.H, d.W = n.data_ptr(), p.data_ptr(), m.data_ptr(), B, H, W
+    d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
+    d.window, d.sigma, d.max_val, d.eps, d.classes = int(window_size), float(sigma), float(max_val), float(eps), int(classes)
+    d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
+    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
+    L.check(be.nirgan_class_metrics(C.byref(d), st), "class_metrics")
     return rows
