@@ -812,10 +812,11 @@ int nirgan_wino6_wgrad_finish_batch(const float* const* slabs, float* const* gra
 int nirgan_bilinear_fwd(const float* src, int B, int SH, int SW, float* dst, int OH, int OW, void* stream);
 int nirgan_bilinear_bwd(const float* ddst, int B, int OH, int OW, float* dsrc, int SH, int SW, void* stream);
 
-/* a = relu(z * (1 + s*e)) ('multiply') or relu(z + s*e) ('add'); z dense [B][H][W][C], e [B][H][W],
- * a written to the interior of a halo'd buffer. */
+/* a = relu(z * (1 + s*e)) ('multiply' with the scale parameter, generator_inject.py:124-125), relu(z * e) ('multiply' with
+ * scale == NULL, :126-127) or relu(z + s*e) ('add', :122-123; s = 1 when scale == NULL); z dense [B][H][W][C], e [B][H][W],
+ * a written to the interior of a halo'd buffer (the halo is left as it is). */
 typedef struct {
-    const float* z; const float* e; const float* scale;   /* scale: 1 float on device */
+    const float* z; const float* e; const float* scale;   /* scale: 1 float on device, or NULL: no scale parameter */
     int style;                                            /* 0 multiply, 1 add */
     int B, H, W, C;
     float* out; int o_hp, o_wp, o_pad;

@@ -123,7 +123,8 @@ __global__ __launch_bounds__(256) void inject_fwd_kernel(const InjP p, int64_t n
         const int h = r / p.W, w = r - h * p.W;
         const float ev = p.e[pix];
         f32x4 v = *reinterpret_cast<const f32x4*>(p.z + pix * p.C + q * 4);
-        if (p.style == 0) v = v * (1.f + s * ev); else v = v + s * ev;
+        // multiply: x * (1 + scale * embeds) with the scale parameter, x * embeds without it (model/generator_inject.py:124-127)
+        if (p.style == 0) v = v * (p.scale ? 1.f + s * ev : ev); else v = v + s * ev;
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
         *reinterpret_cast<f32x4*>(p.out + int64_t(b) * p.o_img + p.o_org + int64_t(h) * p.o_row + int64_t(w) * p.C + q * 4) = v;
@@ -145,6 +146,7 @@ __global__ __launch_bounds__(256) void inject_bwd_kernel(const InjP p, int64_t n
             const int b = int(pix / p.HW), r = int(pix - int64_t(b) * p.HW);
             const int h = r / p.W, w = r - h * p.W;
             const float ev = p.e[pix];
+            const float mul = p.scale ? 1.f + s * ev : ev;          // d a / d z of the multiply style (s == 1 without a scale: de = sum gm z)
             for (int qq = q; qq < p.C / 4; qq += q4) {
                 const f32x4 gv = *reinterpret_cast<const f32x4*>(p.g + pix * p.C + qq * 4);
                 const f32x4 av = *reinterpret_cast<const f32x4*>(p.a + int64_t(b) * p.a_img + p.a_org + int64_t(h) * p.a_row + int64_t(w) * p.C + qq * 4);
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void inject_bwd_kernel(const InjP p, int64_t n
                 for (int k = 0; k < 4; ++k) {
                     gm[k] = av[k] > 0.f ? gv[k] : 0.f;
                     if (p.style == 0) {
-                        dz[k] = gm[k] * (1.f + s * ev);
+                        dz[k] = gm[k] * mul;
                         de_part += gm[k] * zv[k] * s;
                         ds_acc += gm[k] * zv[k] * ev;
                     } else {

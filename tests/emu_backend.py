@@ -1245,6 +1245,10 @@ class EmuBackend:
         # fp32 like the kernel: the indices are singular where pred + band ~ 0 (pred comes out of tanh)
         if not d.rgb and (d.log_all or any(w != 0 for w in (d.w_ndvi, d.w_ndwi, d.w_gndvi, d.w_savi, d.w_msavi, d.w_evi))):
             return self._fail("pix_loss: the spectral indices need rgb")
+        if d.criterion not in (0, 1):
+            return self._fail("pix_loss: criterion must be 0 (l1) or 1 (l2)")
+        if d.extra and not 0 <= d.extra_c < d.extra_cs:
+            return self._fail("pix_loss: extra channel out of range")
         rgb = torch.from_numpy(arr(d.rgb, 3 * n).reshape(B, 3, H, W).copy()) if d.rgb else torch.zeros(B, 3, H, W)
         x = torch.from_numpy(arr(d.nir, n).reshape(B, 1, H, W).copy())
         y = torch.from_numpy(arr(d.pred, n).reshape(B, 1, H, W).copy()).requires_grad_(True)
@@ -1288,8 +1292,10 @@ class EmuBackend:
     def nirgan_adam(self, p, g, m, v, n, lr, b1, b2, eps, step, stream=None):
         self.calls.append("adam")
         P, G_, M, V = arr(p, n), arr(g, n), arr(m, n), arr(v, n)
-        M[:] = M * np.float32(b1) + np.float32(1 - b1) * G_
-        V[:] = V * np.float32(b2) + np.float32(1 - b2) * G_ * G_
+        lr, b1, b2, eps = (float(np.float32(t)) for t in (lr, b1, b2, eps))         # the C ABI takes them as float
+        # 1 - beta from the fp32 beta the entry receives, as the kernel forms it (1.f - b2 is 1.3e-5 below fp32(1 - 0.999))
+        M[:] = M * np.float32(b1) + (np.float32(1) - np.float32(b1)) * G_
+        V[:] = V * np.float32(b2) + (np.float32(1) - np.float32(b2)) * G_ * G_
         bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
         P[:] -= np.float32(lr / bc1) * (M / (np.sqrt(V) / np.float32(np.sqrt(bc2)) + np.float32(eps)))
         return 0
@@ -1317,7 +1323,10 @@ class EmuBackend:
         z = arr(d.z, B * H * W * Cc).reshape(B, H, W, Cc)
         e = arr(d.e, B * H * W).reshape(B, H, W, 1)
         s = arr(d.scale, 1)[0] if d.scale else 1.0
-        v = z * (1 + s * e) if d.style == 0 else z + s * e
+        if d.style == 0:                                     # generator_inject.py:124-127: x * embeds without the scale parameter
+            v = z * (1 + s * e) if d.scale else z * e
+        else:
+            v = z + s * e
         o = arr(d.out, B * d.o_hp * d.o_wp * Cc).reshape(B, d.o_hp, d.o_wp, Cc)
         o[:, d.o_pad:d.o_pad + H, d.o_pad:d.o_pad + W] = np.maximum(v, 0)
         return 0
@@ -1331,9 +1340,13 @@ class EmuBackend:
         z = arr(d.z, B * H * W * Cc).reshape(B, H, W, Cc).astype(np.float64)
         e = arr(d.e, B * H * W).reshape(B, H, W, 1).astype(np.float64)
         s = float(arr(d.scale, 1)[0]) if d.scale else 1.0
+        q4 = min(Cc // 4, 256)
+        blocks = min(-(-B * H * W // (256 // q4)), 2048)
+        if d.dscale and (not d.ws or d.ws_elems < blocks):
+            return self._fail(f"inject_bwd: dscale needs a workspace of {blocks} floats")
         gm = np.where(a > 0, g, 0.0)
         if d.style == 0:
-            dz, de, ds = gm * (1 + s * e), (gm * z * s).sum(-1), (gm * z * e).sum()
+            dz, de, ds = gm * ((1 + s * e) if d.scale else e), (gm * z * s).sum(-1), (gm * z * e).sum()
         else:
             dz, de, ds = gm, (gm * s).sum(-1), (gm * e).sum()
         arr(d.dz, B * H * W * Cc).reshape(B, H, W, Cc)[:] = dz
@@ -1353,6 +1366,8 @@ class EmuBackend:
         return 0
 
     def nirgan_param_scale_bwd(self, gout, x, param, gx, dparam, ws, ws_elems, n, stream=None):
+        if not ws or ws_elems < min(-(-n // 256), 1024):
+            return self._fail("param_scale_bwd: workspace too small")
         g = arr(gout, n)
         arr(gx, n)[:] = g * arr(param, 1)[0]
         arr(dparam, 1)[0] += np.float32(np.dot(g.astype(np.float64), arr(x, n).astype(np.float64)))

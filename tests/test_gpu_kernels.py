@@ -364,7 +364,7 @@ def test_adam_kernel_matches_torch_optimizer():
         close(gp, q.detach(), 1e-6, f"adam step {step}")
 
 
-def test_bilinear_and_inject_match_torch():
+def test_bilinear_resize_matches_torch():
     gen = torch.Generator().manual_seed(8)
     B, S, O_ = 2, 128, 69
     src = torch.randn(B, 1, S, S, generator=gen)
