@@ -268,7 +268,12 @@ int nirgan_instnorm_fwd(const nirgan_in_fwd_desc* d, void* stream);
  *   g_z = g_a * act'(z), z = norm ? (y - mean)*rstd : y;  dy = norm ? rstd*(g_z - mean(g_z) - z*mean(g_z*z)) : g_z.
  * dy is written to the interior (d_pad) of a zero-halo buffer that feeds the data- and
  * weight-gradient GEMMs; gsum_out (optional, dense) receives g_a; dbias (optional, [C])
- * accumulates sum dy.
+ * accumulates sum dy when norm == 0 (it needs ws >= B * nchunk * C floats, one row of channel
+ * sums per block, added in a fixed order).  With norm == 1 the sum of dy over a sample is
+ * exactly 0 (a bias in front of an instance norm has no gradient): dbias is neither read nor
+ * written.  With norm == 1 the two means mean(g_z), mean(g_z * z) of sample b stay in
+ * ws[B * chunks * 2 * C + b * 2 * C ..) as [2][C] (chunks = sums_chunks, or the library's own
+ * count: nirgan_instnorm_ws_elems sizes for it).
  * ------------------------------------------------------------------------------------- */
 typedef struct {
     const float* g; int g_hp, g_wp, g_pad, g_fold;

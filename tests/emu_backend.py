@@ -61,6 +61,15 @@ def mirror_twin(twin_ptr, buf: np.ndarray) -> None:
         t[:] = (bf16_round(buf.reshape(-1)).view(np.uint32) >> 16).astype(np.uint16)
 
 
+def mirror_twin_interior(twin_ptr, buf: np.ndarray, P: int) -> None:
+    """the twin of a halo'd [B][hp][wp][C] buffer whose stores reach the interior only (KEEP border, dy): the twin's halo is not written"""
+    if twin_ptr:
+        t = np.ctypeslib.as_array((C.c_uint16 * buf.size).from_address(int(twin_ptr))).reshape(buf.shape)
+        hp, wp = buf.shape[1], buf.shape[2]
+        inner = np.ascontiguousarray(buf[:, P:hp - P, P:wp - P])
+        t[:, P:hp - P, P:wp - P] = (bf16_round(inner.reshape(-1)).view(np.uint32) >> 16).astype(np.uint16).reshape(inner.shape)
+
+
 def obj(ref):
     return ref._obj if hasattr(ref, "_obj") else ref
 
@@ -957,12 +966,64 @@ class EmuBackend:
             return np.where(z > 0, z, z * slope)
         return z
 
+    @staticmethod
+    def _in_fwd_guard(d):
+        """the argument checks of nirgan_instnorm_fwd (csrc/instnorm.hip), None when the call would launch"""
+        B, H, W, Cc = d.B, d.H, d.W, d.C
+        if not d.y or not (d.out or d.out_bf16 or d.norm):
+            return "in_fwd: null pointer"
+        if B <= 0 or H <= 0 or W <= 0 or Cc < 4 or Cc % 4 or Cc > 1024:
+            return "in_fwd: bad shape"
+        if (d.out or d.out_bf16) and (d.o_pad < 0 or d.o_hp != H + 2 * d.o_pad or d.o_wp != W + 2 * d.o_pad):
+            return "in_fwd: geometry mismatch"
+        if d.border == 1 and (d.o_pad >= H or d.o_pad >= W):
+            return "in_fwd: reflect halo wider than the image"
+        if d.residual and (d.r_hp != H + 2 * d.r_pad or d.r_wp != W + 2 * d.r_pad):
+            return "in_fwd: residual geometry mismatch"
+        if d.out_bf16 and Cc % 8:
+            return "in_fwd: bf16 twin needs C % 8 == 0"
+        if d.norm and not (d.mean and d.rstd and d.ws):
+            return "in_fwd: mean/rstd/ws missing or too small"
+        return None
+
+    @staticmethod
+    def _in_bwd_guard(d):
+        """the argument checks of nirgan_instnorm_bwd, None when the call would launch"""
+        B, H, W, Cc = d.B, d.H, d.W, d.C
+        sums_only = not d.dy and not d.dy_bf16
+        if not (d.dy or d.norm) or not (d.g or d.g2):
+            return "in_bwd: null pointer"
+        if B <= 0 or H <= 0 or W <= 0 or Cc < 4 or Cc % 4 or Cc > 1024:
+            return "in_bwd: bad shape"
+        if d.g and (d.g_hp != H + 2 * d.g_pad or d.g_wp != W + 2 * d.g_pad):
+            return "in_bwd: g geometry mismatch"
+        if d.g_fold and (d.g_pad >= H or d.g_pad >= W):
+            return "in_bwd: fold halo wider than the image"
+        if not sums_only and (d.d_hp != H + 2 * d.d_pad or d.d_wp != W + 2 * d.d_pad):
+            return "in_bwd: dy geometry mismatch"
+        if (d.norm or d.act in (1, 2)) and not d.y:
+            return "in_bwd: y required"
+        if d.norm and not (d.mean and d.rstd and d.ws):
+            return "in_bwd: mean/rstd/ws required when norm"
+        if d.dy_bf16 and Cc % 8:
+            return "in_bwd: bf16 twin needs C % 8 == 0"
+        nchunk = _in_nchunk(B, H * W, Cc)
+        pch = d.sums_chunks if d.norm and d.sums_chunks > 0 else nchunk
+        if d.norm and d.ws_elems < B * pch * 2 * Cc + B * 2 * Cc:
+            return "in_bwd: ws too small"
+        if d.norm and d.sums_chunks > 0 and not d.gsum_out and (not d.g or d.g_fold or d.g2):
+            return "in_bwd: sums_chunks needs gsum_out or a plain g"
+        if not d.norm and d.dbias and (not d.ws or d.ws_elems < B * nchunk * Cc):
+            return "in_bwd: dbias needs ws, too small"
+        return None
+
     def nirgan_instnorm_fwd(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("in_fwd")
         B, H, W, Cc = d.B, d.H, d.W, d.C
-        if d.out and (d.o_hp != H + 2 * d.o_pad or d.o_wp != W + 2 * d.o_pad):
-            return self._fail("in_fwd: geometry")
+        msg = self._in_fwd_guard(d)
+        if msg:
+            return self._fail(msg)
         y = load_y(d.y, B * H * W * Cc, d.y_bf16).reshape(B, H * W, Cc).astype(np.float64)
         if d.norm:
             if d.stats_chunks > 0:
@@ -1005,13 +1066,19 @@ class EmuBackend:
             hh = reflect(np.arange(d.o_hp) - P, H)
             ww = reflect(np.arange(d.o_wp) - P, W)
             out[:] = a[:, hh][:, :, ww]
-        mirror_twin(d.out_bf16, out)      # the device mirrors exactly the stores it makes; untouched (zero) halo stays zero in both
+        if d.border == 1 and P > 0:
+            mirror_twin(d.out_bf16, out)
+        else:
+            mirror_twin_interior(d.out_bf16, out, P)      # the device mirrors exactly the stores it makes: the twin's halo is not written
         return 0
 
     def nirgan_instnorm_bwd(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("in_bwd")
         B, H, W, Cc = d.B, d.H, d.W, d.C
+        msg = self._in_bwd_guard(d)
+        if msg:
+            return self._fail(msg)
         ga = np.zeros((B, H, W, Cc), dtype=np.float64)
         pre = d.norm and d.sums_chunks > 0
         if pre:
@@ -1067,6 +1134,10 @@ class EmuBackend:
                 m1, m2 = psum[:, 0][:, None, :], psum[:, 1][:, None, :]
             dy = rstd * (gzf - m1 - zz * m2)
             dy = dy.reshape(B, H, W, Cc)
+            # the two means stay in ws behind the partial sums, where nirgan_wino6_input_dy_norm reads them
+            pch = d.sums_chunks if pre else _in_nchunk(B, H * W, Cc)
+            mm = arr(d.ws, B * pch * 2 * Cc + B * 2 * Cc)[B * pch * 2 * Cc:].reshape(B, 2, Cc)
+            mm[:, 0], mm[:, 1] = m1[:, 0], m2[:, 0]
         else:
             dy = gz
         if not d.dy and not d.dy_bf16:     # reductions only (with norm): a consumer evaluates dy on the fly; gsum_out was written above
@@ -1075,8 +1146,8 @@ class EmuBackend:
             return self._fail("in_bwd: dy missing")
         o = arr(d.dy, B * d.d_hp * d.d_wp * Cc).reshape(B, d.d_hp, d.d_wp, Cc) if d.dy else np.zeros((B, d.d_hp, d.d_wp, Cc), np.float32)
         o[:, d.d_pad:d.d_pad + H, d.d_pad:d.d_pad + W] = dy
-        mirror_twin(d.dy_bf16, o)
-        if d.dbias:
+        mirror_twin_interior(d.dy_bf16, o, d.d_pad)
+        if d.dbias and not d.norm:         # with norm the sum of dy is exactly 0 and the library leaves dbias untouched
             arr(d.dbias, Cc)[:] += dy.sum((0, 1, 2))
         return 0
 
