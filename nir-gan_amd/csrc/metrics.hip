@@ -6,12 +6,12 @@
 // Per 32x32 output tile: the (32+2r)^2 input patches of both images go to LDS (reflect indexing at the image
 // border), a horizontal pass produces the five filtered moments x, y, x^2, y^2, xy for the (32+2r) x 32 strip,
 // a vertical pass finishes them at the 4 output pixels of each thread.
-#include "common.h"
+#include "ssim_dev.h"
 
 namespace {
 
-constexpr int TILE = 32;
-constexpr int MAXR = 5;                       // window <= 11
+constexpr int TILE = NG_SSIM_TILE;
+constexpr int MAXR = NG_SSIM_MAXR;                       // window <= 11
 constexpr int PW = TILE + 2 * MAXR;           // patch width
 
 struct MetricsP {
@@ -112,13 +112,7 @@ extern "C" int nirgan_image_metrics(const nirgan_metrics_desc* d, void* stream) 
     NG_REQUIRE(d->sigma > 0.f && d->max_val > 0.f, "image_metrics: sigma and max_val must be positive");
     MetricsP p;
     p.a = d->pred; p.b = d->target; p.planes = d->planes; p.H = d->H; p.W = d->W; p.r = r;
-    double sum = 0.0, kv[2 * MAXR + 1];
-    for (int t = 0; t < d->window; ++t) {
-        const double x = double(t - r);
-        kv[t] = exp(-(x * x) / (2.0 * double(d->sigma) * double(d->sigma)));
-        sum += kv[t];
-    }
-    for (int t = 0; t < 2 * MAXR + 1; ++t) p.k[t] = t < d->window ? float(kv[t] / sum) : 0.f;
+    ng_ssim_taps(d->window, d->sigma, p.k);
     p.c1 = (0.01f * d->max_val) * (0.01f * d->max_val);
     p.c2 = (0.03f * d->max_val) * (0.03f * d->max_val);
     p.eps = d->eps;

@@ -1,7 +1,7 @@
-// LDS-staged separable Gaussian of the SSIM map as device functions, used by tilemetrics.hip (one row of metrics per tile).  It is
-// the scheme of metrics.hip (batch means), which keeps its own in-kernel statement: built from these functions its block partial
-// sums came out different in the last bit (another instruction selection of the same expressions), and nirgan_image_metrics
-// must not change.
+// LDS-staged separable Gaussian of the SSIM map as device functions, used by the per-tile entries (tilemetrics.hip,
+// classmetrics.hip).  It is the scheme of metrics.hip (batch means), which keeps its own in-kernel statement: built from these
+// functions its block partial sums came out different in the last bit (another instruction selection of the same expressions), and
+// nirgan_image_metrics must not change.  The host-side taps (ng_ssim_taps) are shared by all of them and by ssimloss.hip.
 //
 // Per 32x32 output tile: the (32+2r)^2 input patches of both images go to LDS (reflect indexing at the border of the
 // REFLECT DOMAIN, an Hd x Wd rectangle whose rows lie `stride` floats apart: the evaluation window inside a stored image --

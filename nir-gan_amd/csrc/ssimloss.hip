@@ -15,12 +15,12 @@
 //   ssim_maps_kernel     S partial sums + the maps a, b, c                      (same tiling as metrics.hip)
 //   ssim_adjoint_kernel  F_m = w (*) zero-padded m on the (H+2r) x (W+2r) domain, m in {a, b, c}
 //   ssim_fold_kernel     grad(q) += -weight/N * (fold F_a + 2 x fold F_b + y fold F_c);  loss += weight (1 - mean S)
-#include "common.h"
+#include "ssim_dev.h"
 
 namespace {
 
-constexpr int TILE = 32;
-constexpr int MAXR = 5;                       // window <= 11
+constexpr int TILE = NG_SSIM_TILE;
+constexpr int MAXR = NG_SSIM_MAXR;                       // window <= 11
 constexpr int PW = TILE + 2 * MAXR;
 
 struct SsimP {
@@ -202,13 +202,7 @@ extern "C" int nirgan_ssim_loss(const nirgan_ssim_loss_desc* d, void* stream) {
     NG_REQUIRE(d->ws_elems >= nirgan_ssim_loss_ws_elems(d->planes, d->H, d->W, d->window), "ssim_loss: workspace too small (nirgan_ssim_loss_ws_elems)");
     SsimP p;
     p.x = d->pred; p.y = d->target; p.planes = d->planes; p.H = d->H; p.W = d->W; p.r = r;
-    double sum = 0.0, kv[2 * MAXR + 1];
-    for (int t = 0; t < d->window; ++t) {
-        const double x = double(t - r);
-        kv[t] = exp(-(x * x) / (2.0 * double(d->sigma) * double(d->sigma)));
-        sum += kv[t];
-    }
-    for (int t = 0; t < 2 * MAXR + 1; ++t) p.k[t] = t < d->window ? float(kv[t] / sum) : 0.f;
+    ng_ssim_taps(d->window, d->sigma, p.k);
     p.c1 = (0.01f * d->max_val) * (0.01f * d->max_val);
     p.c2 = (0.03f * d->max_val) * (0.03f * d->max_val);
     p.eps = d->eps;

@@ -12,13 +12,13 @@
 //   select<2>    counts the next digit of the keys that match a selected prefix; the same one digit further.
 //   finish       narrows the last digit, interpolates rgb_lo / rgb_hi, block 0 of a tile folds the partials in a fixed order and writes
 //                stats, and every block writes its share of rgb_disp.
-// Selection: an order-preserving 32-bit key (windowstats.hip), digits of 11 / 11 / 10 bits, so the rgb is read three times for the
+// Selection: an order-preserving 32-bit key (keys_dev.h), digits of 11 / 11 / 10 bits, so the rgb is read three times for the
 // percentiles.  The FOUR ranks of a tile (floor and ceil of q (n - 1) for q and 1 - q) are narrowed together: a rank whose prefix equals
 // an earlier rank's shares its histogram slot, ranks that part ways (neighbours in different digits, as with a negative and a positive
 // value) get slots of their own, at most four.  Counts are integers, so the selected keys do not depend on the order of arrival.
 // Means: a thread adds its 8 values in index order, a wave adds its lanes by the xor butterfly, the four waves are added in a fixed
 // order, and the block partials are folded the same way: the association depends on (H, W) only.  No float atomics anywhere.
-#include "common.h"
+#include "keys_dev.h"
 
 namespace {
 
@@ -45,11 +45,6 @@ struct PanelP {
     float edges[BINS + 1];
 };
 
-__device__ __forceinline__ float ndvi_value(float n, float r) {
-#pragma clang fp contract(off)
-    return __fdiv_rn(n - r, (n + r) + 1e-6f);   // the association of pix_loss_kernel (losses.hip) and windowstats.hip
-}
-
 __device__ __forceinline__ float clamp01(float v) {          // a NaN and the sign of a zero pass through, as torch.clamp
     v = v < 0.f ? 0.f : v;
     return v > 1.f ? 1.f : v;
@@ -61,15 +56,6 @@ __device__ __forceinline__ float ndvi_disp(float n, float r) {
     v = v < -1.f ? -1.f : v;
     v = v > 1.f ? 1.f : v;
     return (v + 1.f) * 0.5f;
-}
-
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float value_of(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
 
 // values i .. i + 3 of a plane of n values (i a multiple of 4); what lies past n is 0 and ignored by the callers

@@ -11,13 +11,11 @@
 // A window of up to STAGE = 4096 values (the reference's 64 x 64 plot crop is its largest) is read from memory ONCE: the pass that
 // sums the mean leaves the keys in LDS and the four selection passes read LDS.  A larger window is re-read from memory in every pass
 // and its NDVI value recomputed.  That value is bit-identical in every pass because it comes from ONE __device__ function,
-// ndvi_value, whose expression is two additions, one subtraction and one IEEE division (__fdiv_rn; the library is built without
-// fast-math): there is no multiply-add the compiler could contract at one call site and not at another, and contraction is
-// switched off in the function all the same.
+// ndvi_value (keys_dev.h).
 //
 // Means: thread t adds values t, t + 256, ... in order, a wave adds its lanes by the xor butterfly, the four waves are added in a
 // fixed order.  The association depends on (wh, ww) only: a tile's row is bitwise the same alone and inside any stack; no float atomics.
-#include "common.h"
+#include "keys_dev.h"
 
 namespace {
 
@@ -30,20 +28,6 @@ struct WinP {
     int H, W, y0, x0, wh, ww, nq;
     float* rows;
 };
-
-__device__ __forceinline__ float ndvi_value(float n, float r) {
-#pragma clang fp contract(off)
-    return __fdiv_rn(n - r, (n + r) + 1e-6f);   // the association of pix_loss_kernel (losses.hip)
-}
-
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float value_of(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
 
 // value i (row-major inside the window) of this block's quantity; src / red point at the tile's planes, at the window's origin
 __device__ __forceinline__ float value_at(const float* src, const float* red, int W, int ww, int i) {

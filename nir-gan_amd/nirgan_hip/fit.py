@@ -20,6 +20,7 @@ wandb and Lightning loggers stay out of scope.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Callable, Dict, Iterable, Optional
 
 import torch
@@ -38,18 +39,10 @@ def _rank_mean(value: float, device) -> float:
     return value
 
 
-def _write_tile_table(model, val_loader, device, path, crop, epoch):
+def _write_table(evaluate, model, val_loader, device, path, crop, epoch):
     import os
-    from validation_utils.tile_metrics import evaluate_tiles
     stem, ext = os.path.splitext(path)
-    evaluate_tiles(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
-
-
-def _write_land_cover_table(model, val_loader, device, path, crop, epoch):
-    import os
-    from validation_utils.land_cover import evaluate_land_cover
-    stem, ext = os.path.splitext(path)
-    evaluate_land_cover(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
+    evaluate(model, val_loader, crop=crop, device=device, csv_path=f"{stem}_e{epoch}{ext}")
 
 
 def _time_series(model, time_series, device, epoch):
@@ -83,67 +76,72 @@ def _write_figures(model, val_loader, device, figures_dir, epoch, history):
             history["figures"].append(path)
 
 
-def _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                  tile_table_path=None, tile_table_crop=240, time_series=None, time_series_every=1, figures_dir=None, figures_every=1,
-                  land_cover_table_path=None, land_cover_crop=240):
-    """The loop for model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
+def _run_extras(model, val_loader, device, epoch, val_epochs, history, rank0, opts):
+    """What a validation epoch adds beside its scalars, in this order: tile table, land-cover table, time series, figures.  The
+    files are rank 0's to write under data parallel; every rank keeps the time series in its history."""
+    def due(every):
+        return val_epochs % max(int(every), 1) == 0
+    if opts["tile_table_path"] is not None and rank0:
+        from validation_utils.tile_metrics import evaluate_tiles
+        _write_table(evaluate_tiles, model, val_loader, device, opts["tile_table_path"], opts["tile_table_crop"], epoch)
+    if opts["land_cover_table_path"] is not None and rank0:
+        from validation_utils.land_cover import evaluate_land_cover
+        _write_table(evaluate_land_cover, model, val_loader, device, opts["land_cover_table_path"], opts["land_cover_crop"], epoch)
+    if opts["time_series"] is not None and due(opts["time_series_every"]):
+        history["time_series"].append(_time_series(model, opts["time_series"], device, epoch))
+    if opts["figures_dir"] is not None and due(opts["figures_every"]) and rank0:
+        _write_figures(model, val_loader, device, opts["figures_dir"], epoch, history)
+
+
+def _baseline_kind(model, reducer):
+    """model.baseline_models.Linear_NIR / MLP_NIR (train.py:47-54 with --baseline): ONE optimizer, no scheduler
     (baseline_models.py:69-70, :138-139); the checkpoint keeps Lightning's layout with one entry in ``optimizer_states``."""
     if reducer is not None:
         raise NotImplementedError("data-parallel training of the baseline models is not on the MI355X path")
     optim = model.configure_optimizers()
-    history = {"train": [], "val": [], "lr": []}
-    if time_series is not None:
-        history["time_series"] = []
-    if figures_dir is not None:
-        history["figures"] = []
-    step, first_epoch, val_epochs = 0, 0, 0
-    if resume_from is not None:
-        ck = torch.load(resume_from, map_location=device, weights_only=False)
+
+    def restore(ck):
         model.load_state_dict(ck["state_dict"], strict=True)
         model._flat().touch()
         if "optimizer_states" in ck:
             optim.load_state_dict(ck["optimizer_states"][0])
             model.lr = optim.param_groups[0]["lr"]
-        step, first_epoch = int(ck.get("global_step", 0)), int(ck.get("epoch", -1)) + 1
-    for epoch in range(first_epoch, max_epochs):
-        model.train()
-        for batch in train_loader:
-            view = model.train_batch(_to_device(batch, device))
-            if log_every and step % log_every == 0:          # reading the loss synchronises: not every step
-                rec = {"epoch": epoch, "step": step, **view.as_dict()}
-                history["train"].append(rec)
-                if on_log:
-                    on_log(rec)
-            step += 1
-        if val_loader is not None:
-            model.eval()
-            sums, n = {}, 0
-            for i, batch in enumerate(val_loader):
-                model.logged.clear()
-                model.validation_step(_to_device(batch, device), i)
-                for k, v in model.logged.items():
-                    if k.startswith("val/"):
-                        sums[k] = sums.get(k, 0.0) + float(v)
-                n += 1
-            val = {k: v / max(n, 1) for k, v in sums.items()}
-            val["epoch"] = epoch
-            history["val"].append(val)
-            if on_log:
-                on_log(val)
-            if tile_table_path is not None:
-                _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
-            if land_cover_table_path is not None:
-                _write_land_cover_table(model, val_loader, device, land_cover_table_path, land_cover_crop, epoch)
-            if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
-                history["time_series"].append(_time_series(model, time_series, device, epoch))
-            if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0:
-                _write_figures(model, val_loader, device, figures_dir, epoch, history)
-            val_epochs += 1
-        history["lr"].append({"epoch": epoch, "lr": model.lr})
-        if ckpt_path is not None:
-            torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(),
-                        "optimizer_states": [optim.state_dict()], "lr_schedulers": []}, ckpt_path)
-    return history
+    return SimpleNamespace(restore=restore, after_val=lambda val: None, lr=lambda: {"lr": model.lr},
+                           states=lambda: {"optimizer_states": [optim.state_dict()], "lr_schedulers": []})
+
+
+def _px2px_kind(model, reducer):
+    """model.pix2pix.Px2Px_PL: two optimizers (order of configure_optimizers: [D, G], pix2pix.py:490) and ReduceLROnPlateau on
+    ``Schedulers.metric`` for both, interval 'epoch' (pix2pix.py:488-492); the fused trainer takes the learning rates over."""
+    trainer = model.fused_trainer(reducer=reducer)
+    (optim_d, optim_g), scheds = model.configure_optimizers()
+    sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
+    monitor = scheds[0]["monitor"]
+
+    def hand_over():
+        trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
+
+    def restore(ck):
+        model.load_state_dict(ck["state_dict"], strict=False)
+        trainer.flatG.touch()
+        trainer.flatD.touch()
+        if "optimizer_states" in ck:
+            optim_d.load_state_dict(ck["optimizer_states"][0])
+            optim_g.load_state_dict(ck["optimizer_states"][1])
+            hand_over()
+        for sch, sd in zip((sched_d, sched_g), ck.get("lr_schedulers", [])):
+            sch.load_state_dict(sd)
+
+    def after_val(val):
+        if monitor in val:
+            sched_d.step(val[monitor])
+            sched_g.step(val[monitor])
+            hand_over()
+    return SimpleNamespace(restore=restore, after_val=after_val,
+                           lr=lambda: {"lr_d": trainer.lr if trainer.lr_d is None else trainer.lr_d,
+                                       "lr_g": trainer.lr if trainer.lr_g is None else trainer.lr_g},
+                           states=lambda: {"optimizer_states": [optim_d.state_dict(), optim_g.state_dict()],
+                                           "lr_schedulers": [sched_d.state_dict(), sched_g.state_dict()]})
 
 
 def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]] = None, *, max_epochs: int = 1,
@@ -152,7 +150,7 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
         tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1,
         figures_dir: Optional[str] = None, figures_every: int = 1, land_cover_table_path: Optional[str] = None,
         land_cover_crop: Optional[int] = 240) -> Dict[str, list]:
-    """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _fit_baseline).  Returns the history
+    """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _baseline_kind).  Returns the history
     {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
     per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles).
     ``time_series`` (default None: nothing changes): a glob of date rasters (validation_utils.get_pred_nirs_and_info) or a
@@ -165,14 +163,11 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
     which must then carry a ``mask`` of class ids, on the centred ``land_cover_crop`` window as ``<stem>_e<epoch><ext>`` (rank 0 under
     data parallel)."""
     device = device or next(model.parameters()).device
-    if getattr(model, "is_pixel_baseline", False):
-        return _fit_baseline(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from,
-                             tile_table_path, tile_table_crop, time_series, time_series_every, figures_dir, figures_every,
-                             land_cover_table_path, land_cover_crop)
-    trainer = model.fused_trainer(reducer=reducer)
-    (optim_d, optim_g), scheds = model.configure_optimizers()
-    sched_d, sched_g = scheds[0]["scheduler"], scheds[1]["scheduler"]
-    monitor = scheds[0]["monitor"]
+    extras = dict(tile_table_path=tile_table_path, tile_table_crop=tile_table_crop, time_series=time_series,
+                  time_series_every=time_series_every, figures_dir=figures_dir, figures_every=figures_every,
+                  land_cover_table_path=land_cover_table_path, land_cover_crop=land_cover_crop)
+    kind = (_baseline_kind if getattr(model, "is_pixel_baseline", False) else _px2px_kind)(model, reducer)
+    rank0 = reducer is None or getattr(reducer, "rank", 0) == 0
     history = {"train": [], "val": [], "lr": []}
     if time_series is not None:
         history["time_series"] = []
@@ -181,15 +176,7 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
     step, first_epoch, val_epochs = 0, 0, 0
     if resume_from is not None:
         ck = torch.load(resume_from, map_location=device, weights_only=False)
-        model.load_state_dict(ck["state_dict"], strict=False)
-        trainer.flatG.touch()
-        trainer.flatD.touch()
-        if "optimizer_states" in ck:                     # order of configure_optimizers: [D, G] (pix2pix.py:490)
-            optim_d.load_state_dict(ck["optimizer_states"][0])
-            optim_g.load_state_dict(ck["optimizer_states"][1])
-            trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
-        for sch, sd in zip((sched_d, sched_g), ck.get("lr_schedulers", [])):
-            sch.load_state_dict(sd)
+        kind.restore(ck)
         step, first_epoch = int(ck.get("global_step", 0)), int(ck.get("epoch", -1)) + 1
     for epoch in range(first_epoch, max_epochs):
         model.train()
@@ -216,23 +203,10 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
             history["val"].append(val)
             if on_log:
                 on_log(val)
-            if monitor in val:                               # ReduceLROnPlateau, interval 'epoch' (pix2pix.py:488-492)
-                sched_d.step(val[monitor])
-                sched_g.step(val[monitor])
-                trainer.lr_d, trainer.lr_g = optim_d.param_groups[0]["lr"], optim_g.param_groups[0]["lr"]
-            if tile_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
-                _write_tile_table(model, val_loader, device, tile_table_path, tile_table_crop, epoch)
-            if land_cover_table_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
-                _write_land_cover_table(model, val_loader, device, land_cover_table_path, land_cover_crop, epoch)
-            if time_series is not None and val_epochs % max(int(time_series_every), 1) == 0:
-                history["time_series"].append(_time_series(model, time_series, device, epoch))
-            if figures_dir is not None and val_epochs % max(int(figures_every), 1) == 0 and (reducer is None or getattr(reducer, "rank", 0) == 0):
-                _write_figures(model, val_loader, device, figures_dir, epoch, history)
+            kind.after_val(val)
+            _run_extras(model, val_loader, device, epoch, val_epochs, history, rank0, extras)
             val_epochs += 1
-        history["lr"].append({"epoch": epoch, "lr_d": trainer.lr if trainer.lr_d is None else trainer.lr_d,
-                              "lr_g": trainer.lr if trainer.lr_g is None else trainer.lr_g})
-        if ckpt_path is not None and (reducer is None or getattr(reducer, "rank", 0) == 0):
-            torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(),
-                        "optimizer_states": [optim_d.state_dict(), optim_g.state_dict()],
-                        "lr_schedulers": [sched_d.state_dict(), sched_g.state_dict()]}, ckpt_path)
+        history["lr"].append({"epoch": epoch, **kind.lr()})
+        if ckpt_path is not None and rank0:
+            torch.save({"epoch": epoch, "global_step": step, "state_dict": model.state_dict(), **kind.states()}, ckpt_path)
     return history

@@ -25,6 +25,40 @@ import torch
 from nirgan_hip import lib as L
 
 
+def _stream(device):
+    """the current stream's handle on a cuda device; None under the emulator"""
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
+
+
+def _prepare(rgb, nir, pred, lead="B", between=None, also=()):
+    """``(rgb, nir, pred)`` checked and as fp32 contiguous tensors (rgb cut to its first three bands, or None), then ``B, H, W``.
+    ``lead`` names the leading axis in the messages; ``between(B, H, W)`` runs the caller's own checks after the shape checks and
+    before the device check; ``also``: further tensors that must lie on nir's device."""
+    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
+        raise ValueError(f"nir/pred must be equal-shaped [{lead}, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
+    B, _, H, W = nir.shape
+    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
+        raise ValueError(f"rgb must be [{lead}, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
+    if between is not None:
+        between(B, H, W)
+    if (any(t.device != nir.device for t in (pred, *also, *(() if rgb is None else (rgb,))))
+            or (nir.device.type != "cuda" and not L.is_emulated())):
+        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
+    n = nir.detach().to(torch.float32).contiguous()
+    p = pred.detach().to(torch.float32).contiguous()
+    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    return c, n, p, B, H, W
+
+
+def _centre_window(crop, H, W, clip=False):
+    """(y0, x0, ch, cw) of the centred ``crop`` x ``crop`` window (None: the whole image).  Not clipped unless ``clip``: a window
+    larger than the image is the entry's error to raise."""
+    ch, cw = (H, W) if crop is None else (int(crop), int(crop))
+    if clip:
+        ch, cw = min(ch, H), min(cw, W)
+    return (H - ch) // 2, (W - cw) // 2, ch, cw
+
+
 def image_metrics_device(pred: torch.Tensor, target: torch.Tensor, window_size: int = 5, max_val: float = 1.0,
                          sigma: float = 1.5, eps: float = 1e-12) -> torch.Tensor:
     """[mean |d|, mean d^2, mean SSIM map] as a 3-element fp32 tensor on the inputs' device (no host sync)."""
@@ -42,8 +76,7 @@ def image_metrics_device(pred: torch.Tensor, target: torch.Tensor, window_size: 
     d.pred, d.target, d.planes, d.H, d.W = p.data_ptr(), t.data_ptr(), B * Cc, H, W
     d.window, d.sigma, d.max_val, d.eps = int(window_size), float(sigma), float(max_val), float(eps)
     d.ws, d.ws_elems, d.means = ws.data_ptr(), ws.numel(), means.data_ptr()
-    st = torch.cuda.current_stream(p.device).cuda_stream if p.device.type == "cuda" else None
-    L.check(be.nirgan_image_metrics(C.byref(d), st), "image_metrics")
+    L.check(be.nirgan_image_metrics(C.byref(d), _stream(p.device)), "image_metrics")
     return means
 
 
@@ -75,28 +108,18 @@ def tile_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, w
     ``crop_center(.., 240)``; ``None`` = the whole image): SSIM reflects at the window's border, exactly as on a cropped copy,
     but nothing is copied.  ``patch`` is the side of the centred square whose nir / pred means are the last two columns
     (0: NaN); it must fit into the window."""
-    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
-        raise ValueError(f"nir/pred must be equal-shaped [B, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
-    B, _, H, W = nir.shape
-    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
-        raise ValueError(f"rgb must be [B, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
-    if pred.device != nir.device or (rgb is not None and rgb.device != nir.device) or (nir.device.type != "cuda" and not L.is_emulated()):
-        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
-    n = nir.detach().to(torch.float32).contiguous()
-    p = pred.detach().to(torch.float32).contiguous()
-    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
-    ch, cw = (H, W) if crop is None else (int(crop), int(crop))
+    c, n, p, B, H, W = _prepare(rgb, nir, pred)
+    y0, x0, ch, cw = _centre_window(crop, H, W)
     be = L.backend()
     ws = torch.empty(int(be.nirgan_tile_metrics_ws_elems(B, ch, cw)), dtype=torch.float32, device=n.device)
     rows = torch.full((B, L.TILE_METRIC_COLS), float("nan"), dtype=torch.float32, device=n.device)
     d = L.TileMetricsDesc()
     d.rgb = None if c is None else c.data_ptr()
     d.nir, d.pred, d.B, d.H, d.W = n.data_ptr(), p.data_ptr(), B, H, W
-    d.y0, d.x0, d.ch, d.cw = (H - ch) // 2, (W - cw) // 2, ch, cw
+    d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
     d.window, d.sigma, d.max_val, d.eps, d.patch = int(window_size), float(sigma), float(max_val), float(eps), int(patch)
     d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
-    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
-    L.check(be.nirgan_tile_metrics(C.byref(d), st), "tile_metrics")
+    L.check(be.nirgan_tile_metrics(C.byref(d), _stream(n.device)), "tile_metrics")
     return rows
 
 
@@ -112,23 +135,13 @@ def window_stats_device(rgb, nir: torch.Tensor, pred: torch.Tensor, y0: int, x0:
     ``nir`` / ``pred`` are [T, 1, H, W], ``rgb`` [T, 3, H, W] (more bands are cut to the first three) or ``None``: the four NDVI
     columns are then NaN.  The window is rows ``y0 .. y0 + wh``, columns ``x0 .. x0 + ww`` of every tile, applied by indexing.
     The medians are ``torch.median`` of the flattened window (the lower middle value of an even count, NaN with any NaN)."""
-    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
-        raise ValueError(f"nir/pred must be equal-shaped [T, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
-    T, _, H, W = nir.shape
-    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != T or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
-        raise ValueError(f"rgb must be [T, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
-    if pred.device != nir.device or (rgb is not None and rgb.device != nir.device) or (nir.device.type != "cuda" and not L.is_emulated()):
-        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
-    n = nir.detach().to(torch.float32).contiguous()
-    p = pred.detach().to(torch.float32).contiguous()
-    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    c, n, p, T, H, W = _prepare(rgb, nir, pred, lead="T")
     rows = torch.full((T, L.WINDOW_STAT_COLS), float("nan"), dtype=torch.float32, device=n.device)
     d = L.WindowStatsDesc()
     d.rgb = None if c is None else c.data_ptr()
     d.nir, d.pred, d.T, d.H, d.W = n.data_ptr(), p.data_ptr(), T, H, W
     d.y0, d.x0, d.wh, d.ww, d.rows = int(y0), int(x0), int(wh), int(ww), rows.data_ptr()
-    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
-    L.check(L.backend().nirgan_window_stats(C.byref(d), st), "window_stats")
+    L.check(L.backend().nirgan_window_stats(C.byref(d), _stream(n.device)), "window_stats")
     return rows
 
 
@@ -168,23 +181,13 @@ def class_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, mask: torch
     a check that every id inside the evaluation window is integral and in 0..255 (``ValueError`` otherwise; the check reads one
     flag back).  Ids ``>= classes`` belong to no class.  ``crop`` as in ``tile_metrics_device``: the SSIM map is that of the whole
     window, each class takes the mean over its own pixels; a class without pixels has count 0 and NaN elsewhere."""
-    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
-        raise ValueError(f"nir/pred must be equal-shaped [B, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
-    B, _, H, W = nir.shape
-    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
-        raise ValueError(f"rgb must be [B, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
-    if not torch.is_tensor(mask) or tuple(mask.shape) not in ((B, H, W), (B, 1, H, W)) or mask.is_complex():
-        raise ValueError(f"mask must be a [B, H, W] or [B, 1, H, W] tensor of class ids matching nir, got {tuple(getattr(mask, 'shape', ()))}")
-    if not 1 <= int(classes) <= L.CLASS_MAX:
-        raise ValueError(f"classes must lie in 1..{L.CLASS_MAX}, got {classes}")
-    if (pred.device != nir.device or mask.device != nir.device or (rgb is not None and rgb.device != nir.device)
-            or (nir.device.type != "cuda" and not L.is_emulated())):
-        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
-    n = nir.detach().to(torch.float32).contiguous()
-    p = pred.detach().to(torch.float32).contiguous()
-    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
-    ch, cw = (H, W) if crop is None else (int(crop), int(crop))
-    y0, x0 = (H - ch) // 2, (W - cw) // 2
+    def own_checks(B, H, W):
+        if not torch.is_tensor(mask) or tuple(mask.shape) not in ((B, H, W), (B, 1, H, W)) or mask.is_complex():
+            raise ValueError(f"mask must be a [B, H, W] or [B, 1, H, W] tensor of class ids matching nir, got {tuple(getattr(mask, 'shape', ()))}")
+        if not 1 <= int(classes) <= L.CLASS_MAX:
+            raise ValueError(f"classes must lie in 1..{L.CLASS_MAX}, got {classes}")
+    c, n, p, B, H, W = _prepare(rgb, nir, pred, between=own_checks, also=(mask,))
+    y0, x0, ch, cw = _centre_window(crop, H, W)
     m = _mask_uint8(mask.detach().reshape(B, H, W), y0, x0, ch, cw)
     be = L.backend()
     ws = torch.empty(int(be.nirgan_class_metrics_ws_elems(B, ch, cw, int(classes))), dtype=torch.float32, device=n.device)
@@ -195,6 +198,5 @@ def class_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, mask: torch
     d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
     d.window, d.sigma, d.max_val, d.eps, d.classes = int(window_size), float(sigma), float(max_val), float(eps), int(classes)
     d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
-    st = torch.cuda.current_stream(n.device).cuda_stream if n.device.type == "cuda" else None
-    L.check(be.nirgan_class_metrics(C.byref(d), st), "class_metrics")
+    L.check(be.nirgan_class_metrics(C.byref(d), _stream(n.device)), "class_metrics")
     return rows

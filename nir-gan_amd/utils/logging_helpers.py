@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from nirgan_hip import lib as L
+from utils.calculate_metrics import _centre_window, _prepare, _stream
 
 PANEL_OUTPUTS = ("hist", "stats", "nir_disp", "pred_disp", "ndvi_nir_disp", "ndvi_pred_disp", "rgb_disp")
 # column order of nirgan_val_panel stats (include/nirgan_hip.h)
@@ -34,13 +35,10 @@ def figure_crop(H, W):
 
 
 def _window(crop, H, W):
-    if crop is None:
-        return 0, 0, H, W
     if isinstance(crop, (tuple, list)):
         y0, x0, ch, cw = (int(v) for v in crop)
         return y0, x0, ch, cw
-    ch, cw = min(int(crop), H), min(int(crop), W)
-    return (H - ch) // 2, (W - cw) // 2, ch, cw
+    return _centre_window(crop, H, W, clip=True)
 
 
 def panel_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, gain: float = 1.5, perc: float = 2.0,
@@ -51,19 +49,11 @@ def panel_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, gain: fl
     that need it are then left out and columns 6, 7 of ``stats`` are NaN.  ``crop``: ``None`` = the whole image, an int = the side
     of the centred window (clipped to the image), or ``(y0, x0, ch, cw)``.  ``hist`` [B, 2, 100] int32, ``stats`` [B, 8]
     (``PANEL_STAT_COLUMNS``), ``*_disp`` [B, ch, cw], ``rgb_disp`` [B, ch, cw, 3]."""
-    if nir.shape != pred.shape or nir.dim() != 4 or nir.shape[1] != 1:
-        raise ValueError(f"nir/pred must be equal-shaped [B, 1, H, W] tensors, got {tuple(nir.shape)} and {tuple(pred.shape)}")
-    B, _, H, W = nir.shape
-    if rgb is not None and (rgb.dim() != 4 or rgb.shape[0] != B or rgb.shape[1] < 3 or tuple(rgb.shape[2:]) != (H, W)):
-        raise ValueError(f"rgb must be [B, >=3, H, W] matching nir, got {tuple(rgb.shape)}")
-    unknown = set(want) - set(PANEL_OUTPUTS)
-    if unknown:
-        raise ValueError(f"unknown panel outputs {sorted(unknown)}; choose from {PANEL_OUTPUTS}")
-    if pred.device != nir.device or (rgb is not None and rgb.device != nir.device) or (nir.device.type != "cuda" and not L.is_emulated()):
-        raise RuntimeError("nirgan_hip runs on MI355X (cuda device) only; there is no CPU path")
-    n = nir.detach().to(torch.float32).contiguous()
-    p = pred.detach().to(torch.float32).contiguous()
-    c = None if rgb is None else rgb.detach()[:, :3].to(torch.float32).contiguous()
+    def known_outputs(*_):
+        unknown = set(want) - set(PANEL_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown panel outputs {sorted(unknown)}; choose from {PANEL_OUTPUTS}")
+    c, n, p, B, H, W = _prepare(rgb, nir, pred, between=known_outputs)
     y0, x0, ch, cw = _window(crop, H, W)
     dev = n.device
     be = L.backend()
@@ -84,8 +74,7 @@ def panel_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, gain: fl
     d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
     for name, t in out.items():
         setattr(d, name, t.data_ptr())
-    st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
-    L.check(be.nirgan_val_panel(C.byref(d), st), "val_panel")
+    L.check(be.nirgan_val_panel(C.byref(d), _stream(dev)), "val_panel")
     return out
 
 

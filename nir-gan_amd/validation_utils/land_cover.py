@@ -6,18 +6,14 @@ here under the same names in ``utils/``) and no numbers.  ``evaluate_land_cover`
 device pass (utils.calculate_metrics.class_metrics_device) and ONE host copy per batch, one entry per (tile, class) that has pixels.
 ``summarize_land_cover`` pools the table per class over all tiles, weighting each entry by its pixel count.
 """
-import collections
-import csv
-import inspect
+import contextlib
 import math
-import os
 
 import numpy as np
-import torch
 
-from utils.calculate_metrics import CLASS_METRIC_COLUMNS, _mask_uint8, class_metrics_device
+from utils.calculate_metrics import CLASS_METRIC_COLUMNS, _centre_window, _mask_uint8, class_metrics_device
 
-from .tile_metrics import _batches, _items
+from .tile_metrics import _predicted_batches, _write_table
 
 # the legend of the reference's two figures, ids 0..4
 CLC_CLASSES = ("none", "agricultural", "natural vegetation", "water", "artificial")
@@ -26,18 +22,6 @@ CLC_COLORS = ("#ffffff", "#90ee90", "#006400", "#1e90ff", "#ff0000")       # whi
 METRIC_KEYS = ("ssim", "psnr", "l1", "l2", "l1_ndvi", "l1_ndwi", "l1_evi")
 LAND_COVER_KEYS = ("id", "x", "y", "class_id", "class_name", "count") + METRIC_KEYS
 SUMMARY_KEYS = ("class_id", "class_name", "count") + METRIC_KEYS
-
-
-def _with_masks(data, mask_key, queue):
-    """the items of ``data`` unchanged; every tile's mask [H, W] is appended to ``queue`` as its item passes"""
-    for item in _items(data):
-        if mask_key not in item:
-            raise KeyError(f"evaluate_land_cover: a sample without '{mask_key}'")
-        mask = torch.as_tensor(item[mask_key])
-        if torch.as_tensor(item["rgb"]).dim() == 3:
-            mask = mask.unsqueeze(0)
-        queue.extend(mask.reshape(mask.shape[0], *mask.shape[-2:]))
-        yield item
 
 
 def evaluate_land_cover(model, data, classes=CLC_CLASSES, crop=240, batch_size=16, device=None, csv_path=None, mask_key="mask"):
@@ -49,55 +33,33 @@ def evaluate_land_cover(model, data, classes=CLC_CLASSES, crop=240, batch_size=1
     ``model.predict_step(rgb, coords)`` (or a baseline's ``predict_step(rgb)``) runs in eval mode under no_grad and the model's
     mode is restored.  ``crop``: side of the centred evaluation window (None: the whole tile).  ``csv_path``: also write the table
     there, row index first."""
-    device = device or next(model.parameters()).device
     names = tuple(classes)
-    takes_coords = len(inspect.signature(model.predict_step).parameters) >= 2
     table = {k: [] for k in LAND_COVER_KEYS}
-    masks = collections.deque()
     tile = 0
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for rgb, nir, coords in _batches(_with_masks(data, mask_key, masks), int(batch_size)):
-                mask = torch.stack([masks.popleft() for _ in range(rgb.shape[0])])
-                H, W = nir.shape[-2:]
-                ch, cw = (H, W) if crop is None else (int(crop), int(crop))
-                mask = _mask_uint8(mask, (H - ch) // 2, (W - cw) // 2, ch, cw)      # checked where it lies: no device read-back
-                rgb, nir = rgb.to(device), nir.to(device)
-                if takes_coords:
-                    pred = model.predict_step(rgb, None if coords is None else coords.to(device))
-                else:
-                    pred = model.predict_step(rgb)
-                rows = class_metrics_device(rgb, nir, pred, mask.to(device), classes=len(names), crop=crop, window_size=11).cpu()
-                for i in range(rows.shape[0]):
-                    for c, name in enumerate(names):
-                        if rows[i, c, 0] > 0:
-                            table["id"].append(tile)
-                            table["x"].append(float("nan") if coords is None else float(coords[i][0]))
-                            table["y"].append(float("nan") if coords is None else float(coords[i][1]))
-                            table["class_id"].append(c)
-                            table["class_name"].append(name)
-                            table["count"].append(int(rows[i, c, 0]))
-                            for j, key in enumerate(CLASS_METRIC_COLUMNS[1:], start=1):
-                                table[key].append(float(rows[i, c, j]))
-                    tile += 1
-    finally:
-        model.train(was_training)
+    with contextlib.closing(_predicted_batches(model, data, batch_size, device, (mask_key,), "evaluate_land_cover")) as batches:
+        for rgb, nir, coords, pred, mask in batches:
+            mask = _mask_uint8(mask, *_centre_window(crop, *nir.shape[-2:]))      # checked where it lies: no device read-back
+            rows = class_metrics_device(rgb, nir, pred, mask.to(rgb.device), classes=len(names), crop=crop, window_size=11).cpu()
+            for i in range(rows.shape[0]):
+                for c, name in enumerate(names):
+                    if rows[i, c, 0] > 0:
+                        table["id"].append(tile)
+                        table["x"].append(float("nan") if coords is None else float(coords[i][0]))
+                        table["y"].append(float("nan") if coords is None else float(coords[i][1]))
+                        table["class_id"].append(c)
+                        table["class_name"].append(name)
+                        table["count"].append(int(rows[i, c, 0]))
+                        for j, key in enumerate(CLASS_METRIC_COLUMNS[1:], start=1):
+                            table[key].append(float(rows[i, c, j]))
+                tile += 1
     if csv_path is not None:
         write_land_cover_csv(table, csv_path)
     return table
 
 
 def write_land_cover_csv(table, path):
-    """the layout of tile_metrics.write_csv: row index first, floats by repr (they read back exactly)"""
-    folder = os.path.dirname(os.path.abspath(path))
-    os.makedirs(folder, exist_ok=True)
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow([""] + list(LAND_COVER_KEYS))
-        for i in range(len(table["id"])):
-            w.writerow([i] + [repr(table[k][i]) if isinstance(table[k][i], float) else table[k][i] for k in LAND_COVER_KEYS])
+    """the layout of tile_metrics.write_csv"""
+    _write_table(table, LAND_COVER_KEYS, path)
 
 
 def summarize_land_cover(table, max_val=1.0):

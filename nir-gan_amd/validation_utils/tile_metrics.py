@@ -10,6 +10,7 @@ validation_utils/time_series_validation.py:120-132.
 Out of scope: the geo-context join of the table (geopandas: geo_ablation.append_info_to_df / clean_economy), the PNG plots,
 and data-parallel sharding of the table (every process that calls this evaluates all of ``data``).
 """
+import contextlib
 import csv
 import inspect
 import os
@@ -28,8 +29,9 @@ def _items(data):
     return iter(data)
 
 
-def _chunks(data):
-    """every item of ``data`` as a batch (rgb [b,C,H,W], nir [b,1,H,W], coords [b,2] or None): samples get a leading axis"""
+def _chunks(data, extras=(), who="evaluate_tiles"):
+    """every item of ``data`` as a batch (rgb [b,C,H,W], nir [b,1,H,W], coords [b,2] or None, then the per-tile planes under the
+    keys ``extras`` as [b,H,W]): samples get a leading axis"""
     for item in _items(data):
         rgb, nir, coords = torch.as_tensor(item["rgb"]), torch.as_tensor(item["nir"]), item.get("coords")
         if coords is not None:
@@ -37,11 +39,17 @@ def _chunks(data):
         if rgb.dim() == 3:
             rgb, nir = rgb.unsqueeze(0), nir.unsqueeze(0)
             coords = None if coords is None else coords.reshape(1, -1)
-        yield rgb, nir, coords
+        more = []
+        for key in extras:
+            if key not in item:
+                raise KeyError(f"{who}: a sample without '{key}'")
+            t = torch.as_tensor(item[key])
+            more.append(t.reshape(rgb.shape[0], *t.shape[-2:]))
+        yield (rgb, nir, coords, *more)
 
 
-def _batches(data, batch_size):
-    """consecutive equal-shaped tiles regrouped into batches of at most ``batch_size``"""
+def _batches(data, batch_size, extras=(), who="evaluate_tiles"):
+    """consecutive equal-shaped tiles regrouped into batches of at most ``batch_size``; every column of a chunk is cut with its tile"""
     pend, count = [], 0
 
     def key(c):
@@ -49,14 +57,12 @@ def _batches(data, batch_size):
 
     def take(n):
         nonlocal pend, count
-        rgb, nir = torch.cat([c[0] for c in pend]), torch.cat([c[1] for c in pend])
-        coords = None if pend[0][2] is None else torch.cat([c[2] for c in pend])
-        out = (rgb[:n], nir[:n], None if coords is None else coords[:n])
-        pend = [(rgb[n:], nir[n:], None if coords is None else coords[n:])] if count > n else []
+        cols = [None if col[0] is None else torch.cat(col) for col in zip(*pend)]
+        pend = [tuple(None if t is None else t[n:] for t in cols)] if count > n else []
         count -= n
-        return out
+        return tuple(None if t is None else t[:n] for t in cols)
 
-    for c in _chunks(data):
+    for c in _chunks(data, extras, who):
         if pend and key(c) != key(pend[0]):
             while count:
                 yield take(min(count, batch_size))
@@ -68,6 +74,36 @@ def _batches(data, batch_size):
         yield take(min(count, batch_size))
 
 
+def _predict(model, rgb, coords):
+    if len(inspect.signature(model.predict_step).parameters) >= 2:
+        return model.predict_step(rgb, coords)
+    return model.predict_step(rgb)                              # the baselines' signature
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """eval mode under no_grad; the model's train / eval mode is restored"""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
+
+
+def _predicted_batches(model, data, batch_size, device=None, extras=(), who="evaluate_tiles"):
+    """The frame of the evaluation loops: ``data`` regrouped into batches, rgb / nir on ``device`` (default: the model's) and
+    ``pred = model.predict_step(rgb, coords)`` (or a baseline's ``predict_step(rgb)``) in eval mode under no_grad.  Yields
+    ``(rgb, nir, coords, pred, *extras)`` with coords and the extras as they came (on the host).  Close it (``contextlib.closing``)
+    so that the model's mode is restored when the loop ends, however it ends."""
+    device = device or next(model.parameters()).device
+    with _eval_mode(model):
+        for rgb, nir, coords, *more in _batches(data, int(batch_size), extras, who):
+            rgb, nir = rgb.to(device), nir.to(device)
+            yield (rgb, nir, coords, _predict(model, rgb, None if coords is None else coords.to(device)), *more)
+
+
 def evaluate_tiles(model, data, crop=240, batch_size=16, device=None, csv_path=None, patch=32):
     """The validation table of ``data`` under ``model``: a dict of lists with the keys ``TABLE_KEYS``, one entry per tile.
 
@@ -76,43 +112,36 @@ def evaluate_tiles(model, data, crop=240, batch_size=16, device=None, csv_path=N
     (a baseline's ``predict_step(rgb)`` is accepted too) and the model's train / eval mode is restored.  ``crop``: side of the
     centred evaluation window (None: the whole tile); ``patch``: side of the centred square of the patch means, cut to the
     window.  ``csv_path``: also write the table there in the layout of the reference's ``DataFrame.to_csv`` (row index first)."""
-    device = device or next(model.parameters()).device
-    takes_coords = len(inspect.signature(model.predict_step).parameters) >= 2
     table = {k: [] for k in TABLE_KEYS}
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for rgb, nir, coords in _batches(data, int(batch_size)):
-                rgb, nir = rgb.to(device), nir.to(device)
-                if takes_coords:
-                    pred = model.predict_step(rgb, None if coords is None else coords.to(device))
-                else:
-                    pred = model.predict_step(rgb)
-                H, W = nir.shape[-2:]
-                side = min(H, W) if crop is None else int(crop)
-                rows = tile_metrics_device(rgb, nir, pred, crop=crop, window_size=11, patch=min(int(patch), side)).cpu()
-                for i in range(rows.shape[0]):
-                    table["id"].append(len(table["id"]))
-                    table["x"].append(float("nan") if coords is None else float(coords[i][0]))
-                    table["y"].append(float("nan") if coords is None else float(coords[i][1]))
-                    for j, name in enumerate(TILE_METRIC_COLUMNS):
-                        table[name].append(float(rows[i, j]))
-    finally:
-        model.train(was_training)
+    with contextlib.closing(_predicted_batches(model, data, batch_size, device)) as batches:
+        for rgb, nir, coords, pred in batches:
+            H, W = nir.shape[-2:]
+            side = min(H, W) if crop is None else int(crop)
+            rows = tile_metrics_device(rgb, nir, pred, crop=crop, window_size=11, patch=min(int(patch), side)).cpu()
+            for i in range(rows.shape[0]):
+                table["id"].append(len(table["id"]))
+                table["x"].append(float("nan") if coords is None else float(coords[i][0]))
+                table["y"].append(float("nan") if coords is None else float(coords[i][1]))
+                for j, name in enumerate(TILE_METRIC_COLUMNS):
+                    table[name].append(float(rows[i, j]))
     if csv_path is not None:
         write_csv(table, csv_path)
     return table
 
 
-def write_csv(table, path):
+def _write_table(table, keys, path):
+    """row index first, floats by repr (they read back exactly)"""
     folder = os.path.dirname(os.path.abspath(path))
     os.makedirs(folder, exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow([""] + list(TABLE_KEYS))
+        w.writerow([""] + list(keys))
         for i in range(len(table["id"])):
-            w.writerow([i] + [repr(table[k][i]) if isinstance(table[k][i], float) else table[k][i] for k in TABLE_KEYS])
+            w.writerow([i] + [repr(table[k][i]) if isinstance(table[k][i], float) else table[k][i] for k in keys])
+
+
+def write_csv(table, path):
+    _write_table(table, TABLE_KEYS, path)
 
 
 def spider_validation_callback(model, ds, satclip, folder="validation_utils/automated_spiders/", epoch_no=0):

@@ -12,7 +12,6 @@ Raster input: ``root_dir`` may match ``.npy`` files (a ``[4+][H][W]`` array) and
 does not; the ``.tif`` branch is untested in this repository (rasterio is not among its test dependencies).
 """
 import glob
-import inspect
 import io
 import os
 
@@ -20,6 +19,8 @@ import numpy as np
 import torch
 
 from utils.calculate_metrics import window_stats_device
+
+from .tile_metrics import _eval_mode, _predict
 
 PLOT_PATCH_SIZE = 64            # the centre crop every plot and the NDVI window refer to (:169, :225)
 
@@ -50,23 +51,12 @@ def _read_raster(path):
     raise ValueError(f"{path}: unsupported raster format {ext!r} (.npy, .npz, .tif)")
 
 
-def _predict(model, rgb, coords):
-    if len(inspect.signature(model.predict_step).parameters) >= 2:
-        return model.predict_step(rgb, coords)
-    return model.predict_step(rgb)                              # the baselines' signature
-
-
 def predict_stack(model, rgbs, coords=None, batch_size=16):
     """``model.predict_step`` over a [T, 3, H, W] stack in batches of ``batch_size``, eval mode under no_grad, the model's
     train / eval mode restored; the result stays on ``rgbs``' device."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            out = [_predict(model, rgbs[i:i + batch_size], None if coords is None else coords[i:i + batch_size]).float()
-                   for i in range(0, rgbs.shape[0], int(batch_size))]
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        out = [_predict(model, rgbs[i:i + batch_size], None if coords is None else coords[i:i + batch_size]).float()
+               for i in range(0, rgbs.shape[0], int(batch_size))]
     return torch.cat(out)
 
 

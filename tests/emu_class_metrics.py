@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from emu_backend import arr, obj
+from emu_tile_metrics import index_terms, ssim_map, window_cut, window_error
 from emu_val_panel import EmuValPanel
 
 COLS, NV, TILE, CLASS_MAX = 8, 8, 32, 8
@@ -35,54 +36,22 @@ class EmuClassMetrics(EmuValPanel):
     def nirgan_class_metrics(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("class_metrics")
-        if not d.nir or not d.pred or not d.mask or not d.ws or not d.rows:
-            return self._fail("class_metrics: null pointer")
-        if d.B <= 0 or d.H <= 0 or d.W <= 0:
-            return self._fail("class_metrics: empty problem")
+        err = window_error(d, "class_metrics", bool(d.mask))
+        if err:
+            return self._fail(err)
         if d.classes < 1 or d.classes > CLASS_MAX:
             return self._fail("class_metrics: classes must lie in 1..8")
-        if d.window < 1 or d.window > 11 or d.window % 2 == 0:
-            return self._fail("class_metrics: window must be odd and <= 11")
-        r = d.window // 2
-        if d.ch <= 0 or d.cw <= 0 or d.y0 < 0 or d.x0 < 0 or d.y0 + d.ch > d.H or d.x0 + d.cw > d.W:
-            return self._fail("class_metrics: evaluation window outside the image")
-        if d.ch <= r or d.cw <= r:
-            return self._fail("class_metrics: evaluation window smaller than the SSIM window radius")
-        if d.sigma <= 0 or d.max_val <= 0:
-            return self._fail("class_metrics: sigma and max_val must be positive")
-        if d.H * d.W >= 2 ** 31:
-            return self._fail("class_metrics: image too large")
         if d.ch * d.cw >= 2 ** 24:
             return self._fail("class_metrics: evaluation window: the counts are exact as floats below 2^24 only")
         if d.ws_elems < self.nirgan_class_metrics_ws_elems(d.B, d.ch, d.cw, d.classes):
             return self._fail("class_metrics: workspace too small")
-        B, H, W, ch, cw, K = d.B, d.H, d.W, d.ch, d.cw, d.classes
-        win = (slice(None), slice(d.y0, d.y0 + ch), slice(d.x0, d.x0 + cw))
-        n = arr(d.nir, B * H * W).reshape(B, H, W)[win]
-        p = arr(d.pred, B * H * W).reshape(B, H, W)[win]
-        m = bytes_at(d.mask, B * H * W).reshape(B, H, W)[win]
-        x = np.arange(d.window, dtype=np.float64) - r
-        k = np.exp(-x * x / (2.0 * float(d.sigma) ** 2))
-        k = (k / k.sum()).astype(f32)
-
-        def filt(t):                                   # separable, reflect at the WINDOW's border
-            t = np.pad(t, ((0, 0), (r, r), (r, r)), mode="reflect")
-            h = sum(k[i] * t[:, :, i:i + cw] for i in range(d.window))
-            return sum(k[i] * h[:, i:i + ch, :] for i in range(d.window)).astype(f32)
-        c1, c2 = f32((0.01 * d.max_val) ** 2), f32((0.03 * d.max_val) ** 2)
-        mu1, mu2 = filt(n), filt(p)
-        s1, s2, s12 = filt(n * n) - mu1 * mu1, filt(p * p) - mu2 * mu2, filt(n * p) - mu1 * mu2
+        B, H, W, K = d.B, d.H, d.W, d.classes
+        n, p, rgb = window_cut(d)
+        m = bytes_at(d.mask, B * H * W).reshape(B, H, W)[:, d.y0:d.y0 + d.ch, d.x0:d.x0 + d.cw]
         diff = p - n
-        terms = {1: np.abs(diff), 2: diff * diff,
-                 3: ((f32(2) * mu1 * mu2 + c1) * (f32(2) * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2) + f32(d.eps))}
-        if d.rgb:
-            rgb = arr(d.rgb, B * 3 * H * W).reshape(B, 3, H, W)
-            R, G, Bl = (rgb[:, i][win] for i in range(3))
-            e = f32(1e-6)
-            c = (R - f32(7.5)) * (Bl + f32(1))
-            for col, idx in ((5, lambda v: (v - R) / (v + R + e)), (6, lambda v: (v - G) / (v + G + e)),
-                             (7, lambda v: f32(2.5) * ((v - R) / ((v + f32(6)) * c + e)))):
-                terms[col] = np.abs(idx(p) - idx(n))
+        terms = {1: np.abs(diff), 2: diff * diff, 3: ssim_map(n, p, d)}
+        if rgb is not None:
+            terms.update(zip((5, 6, 7), index_terms(n, p, rgb)))
         rows = arr(d.rows, B * K * COLS).reshape(B, K, COLS)
         for b in range(B):
             for cls in range(K):
