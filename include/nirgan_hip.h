@@ -871,6 +871,42 @@ int64_t nirgan_tile_count(int B, int H, int W, int tile, int margin);      /* B 
 int nirgan_tile_gather(const float* scene, int B, int C, int H, int W, int tile, int margin, int first, int n, float* tiles, void* stream);
 int nirgan_tile_scatter(const float* tiles, int B, int C, int H, int W, int tile, int margin, int first, int n, float* scene, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The same tiling with OVERLAPPING usable regions that are cross-faded (every layer of the generator is followed by an instance norm,
+ * so a tile's prediction carries that tile's own per-channel statistics and two neighbours differ by an offset along their border).
+ * Per axis, core = tile - 2*margin and stride = core - overlap with 0 <= overlap <= core/2 (no pixel in more than two usable regions
+ * per axis; overlap = 0 is the tiling above):
+ *   tile i reads scene rows i*stride - margin .. + tile - 1, reflected at the borders (the index rule of the gather above, continued
+ *   with period 2*(H-1) for rows more than one reflection away: a scene may be smaller than a tile);
+ *   its usable region is scene rows [i*stride, i*stride + core) = tile rows [margin, tile - margin);
+ *   tiles per axis: 1 if H <= core, else ceil((H - core) / stride) + 1; numbering b-major, then ti, then tj.
+ * Where two usable regions overlap, band position t = 0 .. overlap-1 counts from the LATER tile's first usable row: the later tile
+ * weighs r(t), the earlier one 1 - r(t); NIRGAN_BLEND_LINEAR: r = (t + 0.5) / overlap, NIRGAN_BLEND_COSINE:
+ * r = 0.5 - 0.5*cos(pi*(t + 0.5) / overlap).  Outside the bands the weight is 1; a pixel's weight for a tile is the product of its row
+ * and column weights, at most four tiles cover a pixel, and their weights sum to 1.
+ *
+ * The gather cuts tiles [first, first + n) out of the scene into tiles [n][C][tile][tile].  The blend adds the usable regions of tiles
+ * [first, first + n) ([n][C][tile][tile]) into scene [B][C][H][W]; pixels past H x W are dropped.  The scene needs NO initialisation:
+ * for each pixel its lowest-numbered covering tile stores w*v and every later covering tile does acc = fma(w, v, acc) in ascending
+ * tile number, one thread per pixel, no atomics.  Launches must come in ascending `first` on one stream and together cover every tile
+ * once; the result is then bitwise independent of how the tiles are split into launches.
+ * Argument errors (null pointer, overlap outside 0 .. core/2, margin >= tile/2, first / n outside the count, unknown window, a plane
+ * of the scene or a tile or the tile count at 2^31 or more) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_BLEND_LINEAR 0
+#define NIRGAN_BLEND_COSINE 1
+typedef struct {
+    int B, C, H, W;                       /* the scene */
+    int tile, margin, overlap;
+    int window;                           /* NIRGAN_BLEND_LINEAR or NIRGAN_BLEND_COSINE (the gather checks it too) */
+    int first, n;                         /* this launch's tiles */
+    float* scene;                         /* [B][C][H][W]: read by the gather, accumulated into by the blend */
+    float* tiles;                         /* [n][C][tile][tile]: written by the gather, read by the blend */
+} nirgan_tile_blend_desc;
+int64_t nirgan_tile_count_ov(int B, int H, int W, int tile, int margin, int overlap);      /* 0 for a bad tiling */
+int nirgan_tile_gather_ov(const nirgan_tile_blend_desc* d, void* stream);
+int nirgan_tile_blend(const nirgan_tile_blend_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,15 +15,22 @@ import torch
 
 
 @torch.no_grad()
-def predict_tiled(model, rgb: torch.Tensor, tile: int = 512, margin: int = 16, batch: int = 8, embeds=None) -> torch.Tensor:
+def predict_tiled(model, rgb: torch.Tensor, tile: int = 512, margin: int = 16, batch: int = 8, embeds=None,
+                  blend: str = "none", overlap=None, window: str = "linear") -> torch.Tensor:
     """rgb: B x 3 x H x W (any H, W >= 4) -> B x 1 x H x W.  ``tile`` is the network input size (multiple of 4);
     ``margin`` pixels on every side of a tile are context only.
 
     On the device the reflect-padded scene is never materialised: one gather launch cuts a batch of overlapping tiles straight out
     of the scene (nirgan_tile_gather reflects at the borders like ``F.pad(mode='reflect')``), the model runs on the batch, one
     scatter launch writes the tiles' cores back (nirgan_tile_scatter) -- no per-tile Python.  Device tensors only (no CPU path; the
-    plain-torch statement of the same tiling lives with the oracle: oracle/nirgan_oracle.py::predict_tiled)."""
+    plain-torch statement of the same tiling lives with the oracle: oracle/nirgan_oracle.py::predict_tiled).
+
+    ``blend="blend"`` lets the tiles' usable regions overlap by ``overlap`` pixels (default ``core // 4``, at most ``core // 2``) and
+    cross-fades them with a ``"linear"`` or ``"cosine"`` ``window``: the generator's instance norms give every tile its own statistics,
+    so neighbouring tiles differ by an offset that ``blend="none"`` leaves as a step on one pixel line."""
     assert tile % 4 == 0 and 0 <= margin < tile // 2
+    if blend != "none":
+        return _predict_blended(model, rgb, tile, margin, batch, embeds, blend, overlap, window)
     B, C3, H, W = rgb.shape
     core = tile - 2 * margin
     from . import lib as L
@@ -49,6 +56,51 @@ def predict_tiled(model, rgb: torch.Tensor, tile: int = 512, margin: int = 16, b
             pred = model(x, embeds.index_select(0, idx))
         pred = pred.detach().to(torch.float32).contiguous()
         L.check(be.nirgan_tile_scatter(pred.data_ptr(), B, 1, H, W, tile, margin, first, n, out.data_ptr(), st), "tile_scatter")
+    return out.to(rgb.dtype)
+
+
+def _predict_blended(model, rgb, tile, margin, batch, embeds, blend, overlap, window):
+    """predict_tiled(blend="blend"): nirgan_tile_gather_ov / model / nirgan_tile_blend per batch of tiles, in ascending tile number on
+    one stream -- the blend entry needs no zeroed output and its result does not depend on ``batch``."""
+    import ctypes as C
+    from . import lib as L
+    if blend != "blend":
+        raise ValueError(f"predict_tiled: blend must be 'none' or 'blend', got {blend!r}")
+    windows = {"linear": L.BLEND_LINEAR, "cosine": L.BLEND_COSINE}
+    if window not in windows:
+        raise ValueError(f"predict_tiled: window must be one of {sorted(windows)}, got {window!r}")
+    B, C3, H, W = rgb.shape
+    core = tile - 2 * margin
+    overlap = core // 4 if overlap is None else int(overlap)
+    if not 0 <= overlap <= core // 2:
+        raise ValueError(f"predict_tiled: overlap {overlap} outside 0 .. core // 2 = {core // 2} (tile {tile}, margin {margin})")
+    if rgb.device.type != "cuda" and not L.is_emulated():
+        raise RuntimeError("predict_tiled runs on MI355X (cuda tensors) only; there is no CPU path")
+    be = L.backend()
+    scene = rgb.detach().to(torch.float32).contiguous()
+    total = int(be.nirgan_tile_count_ov(B, H, W, tile, margin, overlap))
+    if total <= 0:
+        raise ValueError(f"predict_tiled: bad tiling (scene {H}x{W}, tile {tile}, margin {margin}, overlap {overlap})")
+    per_image = total // B
+    out = torch.empty(B, 1, H, W, dtype=torch.float32, device=rgb.device)
+    st = torch.cuda.current_stream(rgb.device).cuda_stream if rgb.device.type == "cuda" else None
+    tiles = torch.empty(min(batch, total), C3, tile, tile, dtype=torch.float32, device=rgb.device)
+    d = L.TileBlendDesc()
+    d.B, d.H, d.W, d.tile, d.margin, d.overlap, d.window = B, H, W, tile, margin, overlap, windows[window]
+    for first in range(0, total, batch):
+        d.first = first
+        d.n = n = min(batch, total - first)
+        d.C, d.scene, d.tiles = C3, scene.data_ptr(), tiles.data_ptr()
+        L.check(be.nirgan_tile_gather_ov(C.byref(d), st), "tile_gather_ov")
+        x = tiles[:n]
+        if embeds is None:
+            pred = model(x)
+        else:
+            idx = torch.arange(first, first + n, device=embeds.device) // per_image      # tile -> scene it was cut from
+            pred = model(x, embeds.index_select(0, idx))
+        pred = pred.detach().to(torch.float32).contiguous()
+        d.C, d.scene, d.tiles = 1, out.data_ptr(), pred.data_ptr()
+        L.check(be.nirgan_tile_blend(C.byref(d), st), "tile_blend")
     return out.to(rgb.dtype)
 
 

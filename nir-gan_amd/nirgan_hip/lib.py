@@ -178,6 +178,14 @@ class HistMatchDesc(C.Structure):
     _fields_ = [("image", fp), ("reference", fp), ("B", i32), ("N", i32), ("ws", fp), ("ws_bytes", i64), ("out", fp)]
 
 
+BLEND_LINEAR, BLEND_COSINE = 0, 1   # include/nirgan_hip.h: NIRGAN_BLEND_LINEAR / _COSINE
+
+
+class TileBlendDesc(C.Structure):
+    _fields_ = [("B", i32), ("C", i32), ("H", i32), ("W", i32), ("tile", i32), ("margin", i32), ("overlap", i32), ("window", i32),
+                ("first", i32), ("n", i32), ("scene", fp), ("tiles", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -228,6 +236,9 @@ PROTOTYPES = {
     "nirgan_tile_count": (i64, [i32, i32, i32, i32, i32]),
     "nirgan_tile_gather": (i32, [fp, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp]),
     "nirgan_tile_scatter": (i32, [fp, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp]),
+    "nirgan_tile_count_ov": (i64, [i32, i32, i32, i32, i32, i32]),
+    "nirgan_tile_gather_ov": (i32, [C.POINTER(TileBlendDesc), fp]),
+    "nirgan_tile_blend": (i32, [C.POINTER(TileBlendDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
