@@ -315,7 +315,9 @@ int nirgan_nchw_to_halo(const float* src, int B, int Cs, int H, int W,
 /* Data gradient of a Conv2d wrt ONE input channel (the generator step only needs dD/dpred, channel 3 of
  * cat(rgb, pred): model/pix2pix.py:216-221 through networks.py:559):
  *   out[b][h][w] = sum_{kh,kw,co} dY[b][(h+pad-kh)/stride][(w+pad-kw)/stride][co] * W[co][channel][kh][kw]
- * dY is a halo'd NHWC buffer [B][OH+2dy_pad][OW+2dy_pad][C]; W is in the reference layout [C][cin][k][k]. */
+ * dY is a halo'd NHWC buffer [B][OH+2dy_pad][OW+2dy_pad][C]; W is in the reference layout [C][cin][k][k].  The halo of dY is never read.
+ * Two kernels: k == 4, stride == 2, pad == 1, H == 2 OH, W == 2 OW and (16 C + 1600) floats of LDS <= 64 KB (C <= 924) take the
+ * output-stationary k4s2 kernel; every other layer the generic one, which needs C % 4 == 0, k <= 7 and k*k*C floats <= 64 KB. */
 typedef struct {
     const float* dy; int dy_hp, dy_wp, dy_pad, C;
     const float* w; int cin, k, stride, pad, channel;
@@ -327,7 +329,10 @@ int nirgan_conv_channel_dgrad(const nirgan_chan_dgrad_desc* d, void* stream);
 /* Single-output-channel convolution tail: out[b][oh][ow] = act(bias + sum_t Q[b][oh+tap_dh[t]][ow+tap_dw[t]][t])
  * restricted to the crop window (crop pixels removed on every side); dst is NCHW [B][1][OH-2crop][OW-2crop].
  * With the 1x1 tap-plane product this is Conv2d(C,1,k) (+Tanh, + crop of pix2pix.py:107-108):
- * model/networks.py:367-368, :579. */
+ * model/networks.py:367-368, :579.  Planes t >= ntaps of Q are never added.
+ * Two kernels: a full k x k tap list in row-major order (tap t = (t / k, t % k)) on a cropped map of >= 4096 outputs takes the rows
+ * kernel (one kernel row of planes in LDS at a time); every other list or map the window kernel, whose all-planes window of
+ * (8 + kh - 1) x (32 + kw - 1) records of (q_cs | 1) floats (kh, kw = 1 + the largest dh, dw) must fit 160 KB of LDS. */
 typedef struct {
     const float* q; int q_hp, q_wp, q_cs;
     int ntaps; int tap_dh[64], tap_dw[64];
@@ -359,8 +364,8 @@ int nirgan_tap_scatter(const nirgan_tap_scatter_desc* d, void* stream);
  * tap-plane route above).  Same results as nirgan_conv_igemm + nirgan_tap_gather /
  * nirgan_tap_scatter + nirgan_wgrad_igemm + nirgan_conv_igemm up to fp32 summation order.
  *   forward : out[b][y][x] = act(bias + sum_{ka,kb,c} x[b][y+crop+ka][x+crop+kb][c] * w[ka*7+kb][c])
- *   dz      : zero-bordered image of dout * act'(out) (workspace shared by the two gradients);
- *             gbias (optional) accumulates sum dz
+ *   dz      : zero-bordered image of dout * act'(out) (workspace shared by the two gradients), [B][OH + 12][S] with
+ *             S = (OW + 12 + 3) / 4 * 4 + 8: nirgan_endconv_dz_elems = B * (OH + 12) * S; gbias (optional) accumulates sum dz
  *   dgrad   : gx over the whole halo'd grid [B][x_hp][x_wp][64]
  *   wgrad   : gw[c*49 + t] (the Conv2d weight's own [1][64][7][7] layout), overwritten; fixed
  *             summation order (bitwise reproducible)

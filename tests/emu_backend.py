@@ -1153,6 +1153,12 @@ class EmuBackend:
 
     # ------------------------------------------------------------------ layout
     def nirgan_nchw_to_halo(self, src, B, Cs, H, W, dst, cs, c0, pad1, pad2, mode, stream=None):
+        if not src or not dst or min(B, Cs, H, W) <= 0:
+            return self._fail("nchw_to_halo: bad arguments")
+        if c0 < 0 or c0 + Cs > cs or pad1 < 0 or pad2 < 0:
+            return self._fail("nchw_to_halo: channel window / pads out of range")
+        if mode == 1 and not (pad1 < H and pad1 < W and pad2 < H + 2 * pad1 and pad2 < W + 2 * pad1):
+            return self._fail("nchw_to_halo: reflect pad wider than the image")
         self.calls.append("nchw_to_halo")
         P = pad1 + pad2
         Hp, Wp = H + 2 * P, W + 2 * P
@@ -1168,10 +1174,18 @@ class EmuBackend:
 
     def nirgan_conv_channel_dgrad(self, ref, stream=None):
         d = obj(ref)
+        if not (d.dy and d.w and d.out):
+            return self._fail("conv_channel_dgrad: null pointer")
+        if d.C < 4 or d.C % 4 or not 1 <= d.k <= 7 or d.stride < 1 or d.pad < 0:
+            return self._fail("conv_channel_dgrad: bad layer")
+        if not 0 <= d.channel < d.cin or min(d.B, d.H, d.W) <= 0 or d.dy_pad < 0:
+            return self._fail("conv_channel_dgrad: bad shape")
         self.calls.append("chan_dgrad")
         OH, OW = (d.H + 2 * d.pad - d.k) // d.stride + 1, (d.W + 2 * d.pad - d.k) // d.stride + 1
         if d.dy_hp != OH + 2 * d.dy_pad or d.dy_wp != OW + 2 * d.dy_pad:
-            return self._fail("chan_dgrad: geometry")
+            return self._fail("conv_channel_dgrad: dY geometry mismatch")
+        if d.k * d.k * d.C * 4 > 65536:
+            return self._fail("conv_channel_dgrad: weights do not fit LDS")
         dy = arr(d.dy, d.B * d.dy_hp * d.dy_wp * d.C).reshape(d.B, d.dy_hp, d.dy_wp, d.C)
         dy = dy[:, d.dy_pad:d.dy_pad + OH, d.dy_pad:d.dy_pad + OW].transpose(0, 3, 1, 2)
         w = arr(d.w, d.C * d.cin * d.k * d.k).reshape(d.C, d.cin, d.k, d.k)[:, d.channel:d.channel + 1]
@@ -1184,6 +1198,20 @@ class EmuBackend:
 
     def nirgan_tap_gather(self, ref, stream=None):
         d = obj(ref)
+        if not (d.q and d.dst):
+            return self._fail("tap_gather: null pointer")
+        if not 1 <= d.ntaps <= 64 or d.ntaps > d.q_cs or d.q_cs % 4:
+            return self._fail("tap_gather: ntaps/q_cs out of range")
+        if d.B <= 0 or d.crop < 0 or d.OH <= 2 * d.crop or d.OW <= 2 * d.crop:
+            return self._fail("tap_gather: bad shape")
+        taps = [(d.tap_dh[t], d.tap_dw[t]) for t in range(d.ntaps)]
+        for t, (dh, dw) in enumerate(taps):
+            if dh < 0 or d.OH - 1 + dh >= d.q_hp or dw < 0 or d.OW - 1 + dw >= d.q_wp:
+                return self._fail(f"tap_gather: tap {t} out of range")
+        kh, kw = max(dh for dh, _ in taps) + 1, max(dw for _, dw in taps) + 1
+        rows = kh == kw and taps == [(t // kw, t % kw) for t in range(kh * kw)] and (d.OH - 2 * d.crop) * (d.OW - 2 * d.crop) >= 4096
+        if not rows and (8 + kh - 1) * (32 + kw - 1) * (d.q_cs | 1) * 4 > 160 * 1024:       # the all-planes window of the library's other kernel
+            return self._fail("tap_gather: window does not fit LDS")
         self.calls.append("tap_gather")
         q = arr(d.q, d.B * d.q_hp * d.q_wp * d.q_cs).reshape(d.B, d.q_hp, d.q_wp, d.q_cs)
         acc = np.zeros((d.B, d.OH, d.OW), dtype=np.float64)
@@ -1221,7 +1249,8 @@ class EmuBackend:
         return B * (OH + 12) * ((OW + 12 + 3) // 4 * 4 + 8) if min(B, OH, OW) > 0 else 0
 
     def nirgan_endconv_ws_elems(self, B, OH, OW):
-        return min((B * (OH + 6) + 3) // 4, 512) * 49 * 64 if min(B, OH) > 0 else 0
+        # the library's figure: one [49][64] partial per weight-gradient block + the 1024 per-block bias-gradient partials of the dz pass
+        return min((B * (OH + 6) + 3) // 4, 512) * 49 * 64 + 1024 if min(B, OH) > 0 else 0
 
     def _endconv(self, ref, what):
         d = obj(ref)
@@ -1258,6 +1287,10 @@ class EmuBackend:
         d, rc = self._endconv(ref, "endconv_dz")
         if d is None:
             return rc
+        if d.dz_elems < self.nirgan_endconv_dz_elems(d.B, d.OH, d.OW):
+            return self._fail("endconv_dz: workspace too small or unaligned")
+        if d.gbias and (not d.ws or d.ws_elems < self.nirgan_endconv_ws_elems(d.B, d.OH, d.OW)):
+            return self._fail("endconv_dz: gbias needs the partials workspace (nirgan_endconv_ws_elems)")
         c = d.crop
         H2, W2 = d.OH - 2 * c, d.OW - 2 * c
         dz = arr(d.dout, d.B * H2 * W2).reshape(d.B, H2, W2).astype(np.float64)
@@ -1274,6 +1307,8 @@ class EmuBackend:
         d, rc = self._endconv(ref, "endconv_dgrad")
         if d is None:
             return rc
+        if d.dz_elems < self.nirgan_endconv_dz_elems(d.B, d.OH, d.OW):
+            return self._fail("endconv_dgrad: workspace too small or unaligned")
         img = self._endconv_dz_image(d).astype(np.float64)
         w = arr(d.w, 49 * 64).reshape(7, 7, 64).astype(np.float64)
         gx = np.zeros((d.B, d.x_hp, d.x_wp, 64))
@@ -1287,6 +1322,10 @@ class EmuBackend:
         d, rc = self._endconv(ref, "endconv_wgrad")
         if d is None:
             return rc
+        if d.dz_elems < self.nirgan_endconv_dz_elems(d.B, d.OH, d.OW):
+            return self._fail("endconv_wgrad: dz workspace too small or unaligned")
+        if not d.ws or d.ws_elems < self.nirgan_endconv_ws_elems(d.B, d.OH, d.OW):
+            return self._fail("endconv_wgrad: partials workspace too small")
         img = self._endconv_dz_image(d).astype(np.float64)
         x = arr(d.x, d.B * d.x_hp * d.x_wp * 64).reshape(d.B, d.x_hp, d.x_wp, 64).astype(np.float64)
         gw = np.zeros((7, 7, 64))
