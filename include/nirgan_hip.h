@@ -912,6 +912,35 @@ int64_t nirgan_tile_count_ov(int B, int H, int W, int tile, int margin, int over
 int nirgan_tile_gather_ov(const nirgan_tile_blend_desc* d, void* stream);
 int nirgan_tile_blend(const nirgan_tile_blend_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Dihedral test-time augmentation of tiles: the generator's prediction depends on a tile's orientation, so the k = 1, 2, 4 or 8
+ * mirrored / transposed views of every tile are predicted, placed back and averaged (self-ensembling over a subgroup of D4).
+ * View g (0 <= g < k) of an H x W plane x is built from three bits -- bit 0 mirrors columns, bit 1 mirrors rows, bit 2 transposes:
+ *     view_g(x)[i][j] = x[i'][j']   with   (a, b) = (j, i) if bit 2 is set, else (i, j);
+ *                                          i' = H-1-a if bit 1 is set, else a;   j' = W-1-b if bit 0 is set, else b.
+ * k = 2 is {identity, column mirror}, k = 4 the four flips, k = 8 all of D4 (needs H == W).  Views 0 .. 3 are involutions; so are
+ * 4 and 7 (the two diagonal reflections), while 5 and 6 (the quarter turns) are each other's inverse.
+ *
+ * Expand copies:  src [n][C][H][W] -> dst [n][k][C][H][W],  dst[t][g][c] = view_g(src[t][c]).  A pure permutation, bitwise exact
+ * (NaN payloads included).
+ * Merge undoes and averages:  src [n][k][C][H][W] -> dst [n][C][H][W],  dst[t][c] = (1/k) * sum over g of v_g with
+ * v_g = view_g^-1(src[t][g][c]) (v_g[i'][j'] = src[t][g][c][i][j] in the terms above).  The additions are plain fp32 adds (no fma) in
+ * the fixed pairwise tree ((v0+v1)+(v2+v3))+((v4+v5)+(v6+v7)), or its prefix v0, v0+v1, (v0+v1)+(v2+v3) for k = 1, 2, 4, followed by
+ * ONE multiply by 1/k (a power of two: exact).  k equal inputs therefore give exactly that value, and merge(expand(x)) == x
+ * bitwise for finite x.
+ * No atomics; every destination element is written by one thread, so neither dst needs initialisation.  One launch per call.
+ * Argument errors (null pointer, views not 1 / 2 / 4 / 8, views == 8 with H != W, a non-positive extent, a plane H*W or the plane
+ * count n*views*C at 2^31 or more) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    int n, C, H, W;                       /* n images of C planes of H x W */
+    int views;                            /* k = 1, 2, 4 or 8; k = 8 needs H == W */
+    const float* src;
+    float* dst;
+} nirgan_tile_views_desc;
+int nirgan_tile_views_expand(const nirgan_tile_views_desc* d, void* stream);      /* src [n][C][H][W] -> dst [n][k][C][H][W] */
+int nirgan_tile_views_merge(const nirgan_tile_views_desc* d, void* stream);       /* src [n][k][C][H][W] -> dst [n][C][H][W] */
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,13 @@ class TileBlendDesc(C.Structure):
                 ("first", i32), ("n", i32), ("scene", fp), ("tiles", fp)]
 
 
+TTA_VIEWS = {"none": 1, "flip": 2, "flips": 4, "d4": 8}   # include/nirgan_hip.h: nirgan_tile_views_desc.views
+
+
+class TileViewsDesc(C.Structure):
+    _fields_ = [("n", i32), ("C", i32), ("H", i32), ("W", i32), ("views", i32), ("src", fp), ("dst", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -239,6 +246,8 @@ PROTOTYPES = {
     "nirgan_tile_count_ov": (i64, [i32, i32, i32, i32, i32, i32]),
     "nirgan_tile_gather_ov": (i32, [C.POINTER(TileBlendDesc), fp]),
     "nirgan_tile_blend": (i32, [C.POINTER(TileBlendDesc), fp]),
+    "nirgan_tile_views_expand": (i32, [C.POINTER(TileViewsDesc), fp]),
+    "nirgan_tile_views_merge": (i32, [C.POINTER(TileViewsDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
