@@ -941,6 +941,75 @@ typedef struct {
 int nirgan_tile_views_expand(const nirgan_tile_views_desc* d, void* stream);      /* src [n][C][H][W] -> dst [n][k][C][H][W] */
 int nirgan_tile_views_merge(const nirgan_tile_views_desc* d, void* stream);       /* src [n][k][C][H][W] -> dst [n][C][H][W] */
 
+/* ---------------------------------------------------------------------------------------
+ * The geo-context join of the validation table (validation_utils/geo_ablation.py:18-53 of the reference: gpd.sjoin of every tile's
+ * lon / lat with a country layer, a point query of a Koeppen raster): n_points points against a polygon layer, and against a raster.
+ * Planar coordinates, float64 throughout; no antimeridian wrapping, no geodesic edges.
+ *
+ * The layer: verts [n_verts][2] (x, y); ring r owns vertices ring_start[r] .. ring_start[r+1]-1 (ring_start[0] = 0,
+ * ring_start[n_rings] = n_verts) and the closing edge from its last vertex to its first -- a ring that repeats its first vertex at
+ * the end is legal too, the zero-length edge never counts; ring_region[r] in 0 .. n_regions-1, NON-DECREASING, names the region
+ * (feature) of ring r: holes and the parts of a multipolygon are further rings of the same region.  region_box [n_regions][4] =
+ * (xmin, ymin, xmax, ymax) over the region's vertices, (+inf, +inf, -inf, -inf) for a region without vertices:
+ * nirgan_region_boxes WRITES it (once per layer), nirgan_point_regions reads it.
+ *
+ * nirgan_point_regions: region[i] = the LOWEST region index whose rings are crossed an odd number of times in total by the ray from
+ * point i towards +x, or -1 (the even-odd rule: a point in a hole is outside; an enclave listed after the country around it is found
+ * through that country's hole; where regions overlap the lowest index wins).  An edge (x0,y0) -> (x1,y1) is crossed by (px,py) iff
+ *     straddles = (y0 > py) != (y1 > py)
+ *     d         = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0)
+ *     crossing  = straddles && (y1 > y0 ? d > 0 : d < 0)
+ * with every operation an individually rounded float64 operation (four subtractions, two products, one subtraction; no fused
+ * multiply-add, no division): the result is bitwise that statement's, for every point.  A point exactly on an edge (d == 0) does not
+ * cross that edge; its membership is whatever follows and is UNSPECIFIED.  Finite vertices are assumed; a point with a NaN gets -1.
+ * The parities are combined with integer XOR in a uint32 bitset ws [n_points][ceil(n_regions / 32)] which the entry zeroes itself:
+ * the result does not depend on slab_verts (vertices per LDS slab, 0 = the default, at most NIRGAN_GEO_SLAB_MAX; the edge axis is
+ * cut at slab boundaries, also across blocks when there are few points), nor on the order of anything.  No float atomics.
+ * n_points == 0 or n_regions == 0 returns NIRGAN_OK without a launch (n_regions == 0 leaves `region` untouched: fill it with -1).
+ * Argument errors return NIRGAN_ERR_ARG before any launch: a null pointer, a negative count, slab_verts out of range, a workspace
+ * below nirgan_point_regions_ws_bytes, and -- where the optional HOST copies ring_start_host / ring_region_host are given (device
+ * memory is not read for checks) -- a decreasing ring_region or ring_start, a region id outside the layer, ring_start[0] != 0 or
+ * ring_start[n_rings] != n_verts.  Without them a malformed table gives garbage but reads and writes nothing out of range.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_GEO_SLAB_MAX 2048
+typedef struct {
+    const double* points;                 /* [n_points][2]; not read by nirgan_region_boxes */
+    int n_points;
+    int n_verts;
+    const double* verts;                  /* [n_verts][2] */
+    const int32_t* ring_start;            /* [n_rings + 1] */
+    const int32_t* ring_region;           /* [n_rings] */
+    int n_rings, n_regions;
+    double* region_box;                   /* [n_regions][4] */
+    const int32_t* ring_start_host;       /* optional HOST copies of the two tables, checked before any launch */
+    const int32_t* ring_region_host;
+    int slab_verts;                       /* 0 = the default; 1 .. NIRGAN_GEO_SLAB_MAX */
+    uint32_t* ws;                         /* nirgan_point_regions_ws_bytes(n_points, n_regions) bytes, zeroed by the entry */
+    int64_t ws_bytes;
+    int32_t* region;                      /* [n_points], OVERWRITTEN (unless n_regions == 0) */
+} nirgan_point_regions_desc;
+int64_t nirgan_point_regions_ws_bytes(int n_points, int n_regions);      /* n_points * ceil(n_regions / 32) * 4; 0 for an empty problem */
+int nirgan_region_boxes(const nirgan_point_regions_desc* d, void* stream);
+int nirgan_point_regions(const nirgan_point_regions_desc* d, void* stream);
+
+/* value[i] = raster[row][col] with col = floor((x - x0) / dx), row = floor((y - y0) / dy) in float64 (a north-up affine transform,
+ * dy may be negative): the cell that CONTAINS the point, no interpolation.  0 outside the raster, for a NaN coordinate, or where the
+ * cell equals `nodata` (has_nodata != 0) -- the reference's "Unknown" id.  dx or dy of 0, a NaN in the transform, an empty raster, an
+ * unknown dtype, a negative count or a null pointer return NIRGAN_ERR_ARG before any launch; n_points == 0 launches nothing. */
+#define NIRGAN_RASTER_U8 0
+#define NIRGAN_RASTER_I16 1
+#define NIRGAN_RASTER_I32 2
+typedef struct {
+    const double* points;                 /* [n_points][2] */
+    int n_points;
+    int H, W, dtype;                      /* NIRGAN_RASTER_* */
+    const void* raster;                   /* [H][W] */
+    double x0, dx, y0, dy;
+    int has_nodata, nodata;
+    int32_t* value;                       /* [n_points], OVERWRITTEN */
+} nirgan_raster_lookup_desc;
+int nirgan_raster_lookup(const nirgan_raster_lookup_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

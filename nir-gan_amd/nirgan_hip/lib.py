@@ -193,6 +193,22 @@ class TileViewsDesc(C.Structure):
     _fields_ = [("n", i32), ("C", i32), ("H", i32), ("W", i32), ("views", i32), ("src", fp), ("dst", fp)]
 
 
+GEO_SLAB_MAX = 2048                                       # include/nirgan_hip.h: NIRGAN_GEO_SLAB_MAX
+RASTER_U8, RASTER_I16, RASTER_I32 = 0, 1, 2               # include/nirgan_hip.h: NIRGAN_RASTER_*
+
+
+class PointRegionsDesc(C.Structure):
+    _fields_ = [("points", fp), ("n_points", i32), ("n_verts", i32), ("verts", fp), ("ring_start", fp), ("ring_region", fp),
+                ("n_rings", i32), ("n_regions", i32), ("region_box", fp), ("ring_start_host", fp), ("ring_region_host", fp),
+                ("slab_verts", i32), ("ws", fp), ("ws_bytes", i64), ("region", fp)]
+
+
+class RasterLookupDesc(C.Structure):
+    _fields_ = [("points", fp), ("n_points", i32), ("H", i32), ("W", i32), ("dtype", i32), ("raster", fp),
+                ("x0", C.c_double), ("dx", C.c_double), ("y0", C.c_double), ("dy", C.c_double),
+                ("has_nodata", i32), ("nodata", i32), ("value", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -248,6 +264,10 @@ PROTOTYPES = {
     "nirgan_tile_blend": (i32, [C.POINTER(TileBlendDesc), fp]),
     "nirgan_tile_views_expand": (i32, [C.POINTER(TileViewsDesc), fp]),
     "nirgan_tile_views_merge": (i32, [C.POINTER(TileViewsDesc), fp]),
+    "nirgan_point_regions_ws_bytes": (i64, [i32, i32]),
+    "nirgan_region_boxes": (i32, [C.POINTER(PointRegionsDesc), fp]),
+    "nirgan_point_regions": (i32, [C.POINTER(PointRegionsDesc), fp]),
+    "nirgan_raster_lookup": (i32, [C.POINTER(RasterLookupDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),

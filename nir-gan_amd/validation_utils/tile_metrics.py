@@ -7,8 +7,11 @@ copies; here tiles are batched, the crop is an index window and every batch is O
 tile_metrics_device) and ONE host copy.  Two more columns, the nir / pred means of a centred patch, restate the centroid values of
 validation_utils/time_series_validation.py:120-132.
 
-Out of scope: the geo-context join of the table (geopandas: geo_ablation.append_info_to_df / clean_economy), the PNG plots,
-and data-parallel sharding of the table (every process that calls this evaluates all of ``data``).
+The geo-context join of the table (countries, continents, economies, Koeppen classes) is validation_utils/geo_ablation.py, the
+radar charts drawn from it validation_utils/plot_val_spiders.py; ``spider_validation_callback`` runs the join and writes the
+reference's GeoJSON when it is given the layers.
+
+Out of scope: data-parallel sharding of the table (every process that calls this evaluates all of ``data``).
 """
 import contextlib
 import csv
@@ -144,8 +147,18 @@ def write_csv(table, path):
     _write_table(table, TABLE_KEYS, path)
 
 
-def spider_validation_callback(model, ds, satclip, folder="validation_utils/automated_spiders/", epoch_no=0):
-    """The reference's callback (validation_utils/spider_validation_callback.py:13) up to its table: evaluates ``ds`` and writes
-    ``<folder>/validation_metrics.csv``; returns the table.  ``satclip`` and ``epoch_no`` only name the reference's GeoJSON,
-    which needs the geo-context join and is not written here."""
-    return evaluate_tiles(model, ds, crop=240, csv_path=os.path.join(folder, "validation_metrics.csv"))
+def spider_validation_callback(model, ds, satclip, folder="validation_utils/automated_spiders/", epoch_no=0, world=None, koppen=None,
+                               legend=None):
+    """The reference's callback (validation_utils/spider_validation_callback.py:13): evaluates ``ds`` and writes
+    ``<folder>/validation_metrics.csv``.  Without ``world`` that is all, and the table is returned.  With ``world`` (a
+    ``geo_ablation.PolygonLayer``; ``koppen``: a ``RasterLayer``, ``legend``: its id -> code legend) the table is joined to the
+    layers (``append_info_to_df``), its economy column cleaned (``clean_economy``) and written as
+    ``<folder>/validation_metrics_ablation_satclip_<satclip>_e<epoch_no>.geojson``, the reference's name; the joined table is
+    returned."""
+    table = evaluate_tiles(model, ds, crop=240, csv_path=os.path.join(folder, "validation_metrics.csv"))
+    if world is None:
+        return table
+    from .geo_ablation import append_info_to_df, clean_economy, write_geojson
+    joined = clean_economy(append_info_to_df(table, world, koppen, legend))
+    write_geojson(joined, os.path.join(folder, "validation_metrics_ablation_satclip_" + str(satclip) + "_e" + str(epoch_no) + ".geojson"))
+    return joined
