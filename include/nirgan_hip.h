@@ -398,6 +398,23 @@ int nirgan_endconv_wgrad(const nirgan_endconv_desc* d, void* stream);
 int nirgan_lsgan(const float* pred, int64_t n, float target, float weight,
                  float* loss_out, float* grad, void* stream);
 
+/* The other two objectives of GANLoss (model/networks.py:210-276), value and gradient in one pass like nirgan_lsgan: loss_out[0] is
+ * accumulated (one add per launch), grad [n] is overwritten and may be NULL (forward only).  One workgroup; the terms are summed in
+ * float64 in a fixed order, so two runs give the same bits.  pred needs no alignment, n >= 1 is any.
+ *   NIRGAN_GAN_VANILLA  BCEWithLogitsLoss against the label, x = pred[i], t = target (any float: checkpoints may carry smoothed labels):
+ *                       loss_out[0] += weight * mean(max(x, 0) - x t + log1p(exp(-|x|)))
+ *                       grad[i]      = weight * (sigmoid(x) - t) * (1.f / (float)n),  sigmoid from exp(-|x|): 1 / (1 + e) for x >= 0,
+ *                                      e / (1 + e) below; precise expf / log1pf, no exp of a positive argument
+ *   NIRGAN_GAN_WGANGP   s = target > 0.5f ? -1 : +1 (the label only picks the side, as target_is_real does):
+ *                       loss_out[0] += weight * s * mean(x)
+ *                       grad[i]      = (s * weight) * (1.f / (float)n), both operations in fp32
+ * Any other mode (lsgan keeps nirgan_lsgan), n <= 0, a NULL pred or loss_out: NIRGAN_ERR_ARG before any launch.
+ * cal_gradient_penalty (networks.py:279-313) is not part of the entry. */
+#define NIRGAN_GAN_VANILLA 1
+#define NIRGAN_GAN_WGANGP 2
+int nirgan_gan_loss(const float* pred, int64_t n, int mode, float target, float weight,
+                    float* loss_out, float* grad, void* stream);
+
 /* L1 + spectral-index losses on NCHW tiles (rgb [B][3][H][W], nir/pred [B][1][H][W]).
  *   sums[0..6] += sum|pred-nir|, then the per-index sums of criterion(idx(nir), idx(pred))
  *   for ndvi, ndwi, gndvi, savi, msavi, evi (all divided by n by the caller);

@@ -1,7 +1,8 @@
 // LSGAN, L1 and spectral-index (NDVI/NDWI/GNDVI/SAVI/MSAVI/EVI) losses: value and gradient
 // wrt the prediction in one streaming pass over NCHW tiles.  HBM-bound.  No float atomics between blocks: LSGAN (a few 10^4 patch
 // values) is ONE block; the pixel losses leave per-block partial sums in a workspace that ng_partials_finish adds up in block order,
-// so the loss scalars are bitwise reproducible.
+// so the loss scalars are bitwise reproducible.  The vanilla (BCE with logits) and wgangp objectives share one kernel of the same shape
+// whose partial sums are float64.
 #include "common.h"
 
 namespace {
@@ -47,6 +48,51 @@ __global__ __launch_bounds__(1024) void lsgan_kernel(const float* __restrict__ p
     block_partials<1>(acc, total);
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(loss_out, total[0]);          // ONE add per launch: commutes with another stream's
+}
+
+// GANLoss('vanilla') / GANLoss('wgangp'): one block of 1024 threads like lsgan_kernel, scalar loads (any alignment, any n >= 1, the
+// tail predicated).  Every term is formed in fp32 from the overflow-safe forms (exp only of -|x|) and summed in float64: thread,
+// then wave (xor butterfly), then the waves in ascending order -- one association for every launch.
+template <int MODE>
+__global__ __launch_bounds__(1024) void gan_loss_kernel(const float* __restrict__ pred, int64_t n, float target, float weight,
+                                                        float* loss_out, float* __restrict__ grad) {
+    const float inv = 1.f / float(n);
+    const float sw = target > 0.5f ? -weight : weight;           // wgangp: the side of the label only
+    double acc = 0.0;
+    for (int64_t i0 = threadIdx.x; i0 < n; i0 += 4096) {
+        float x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t i = i0 + j * 1024;
+            x[j] = i < n ? pred[i] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t i = i0 + j * 1024;
+            if (i >= n) continue;
+            if (MODE == NIRGAN_GAN_VANILLA) {
+                const float e = expf(-fabsf(x[j]));              // in (0, 1]: never overflows
+                const float r = 1.f / (1.f + e);
+                const float sig = x[j] >= 0.f ? r : e * r;
+                acc += (double(fmaxf(x[j], 0.f)) - double(x[j]) * double(target)) + double(log1pf(e));
+                if (grad) grad[i] = weight * (sig - target) * inv;
+            } else {
+                acc += double(x[j]);
+                if (grad) grad[i] = sw * inv;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double part[16];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < 16; ++w) t += part[w];
+        t = t / double(n) * double(MODE == NIRGAN_GAN_VANILLA ? weight : sw);
+        atomicAdd(loss_out, float(t));                            // ONE add per launch: commutes with another stream's
+    }
 }
 
 struct PixP {
@@ -142,6 +188,17 @@ extern "C" int nirgan_lsgan(const float* pred, int64_t n, float target, float we
     NG_REQUIRE(pred && loss_out && n > 0, "lsgan: bad arguments");
     hipLaunchKernelGGL(lsgan_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), pred, n, target, weight, loss_out, grad);
     return nirgan_check_launch("lsgan");
+}
+
+extern "C" int nirgan_gan_loss(const float* pred, int64_t n, int mode, float target, float weight, float* loss_out, float* grad,
+                               void* stream) {
+    NG_REQUIRE(mode == NIRGAN_GAN_VANILLA || mode == NIRGAN_GAN_WGANGP, "gan_loss: mode must be 1 (vanilla) or 2 (wgangp); lsgan has nirgan_lsgan");
+    NG_REQUIRE(pred && loss_out && n > 0, "gan_loss: bad arguments");
+    if (mode == NIRGAN_GAN_VANILLA)
+        hipLaunchKernelGGL(gan_loss_kernel<NIRGAN_GAN_VANILLA>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), pred, n, target, weight, loss_out, grad);
+    else
+        hipLaunchKernelGGL(gan_loss_kernel<NIRGAN_GAN_WGANGP>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), pred, n, target, weight, loss_out, grad);
+    return nirgan_check_launch("gan_loss");
 }
 
 extern "C" int nirgan_pix_loss(const nirgan_pix_loss_desc* d, void* stream) {

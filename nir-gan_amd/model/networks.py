@@ -8,8 +8,10 @@ are parameter containers: ``forward`` runs the hand-written HIP engines of ``nir
 (there is no torch.nn compute and no CPU fallback).
 
 Supported on this path: ``netG`` resnet_6blocks / resnet_9blocks, ``netD`` basic / n_layers(3),
-``norm='instance'``, no dropout, ``gan_mode='lsgan'`` -- everything the shipped configs select
-(configs/config_px2px.yaml:13-21).  Other names the reference knows raise NotImplementedError.
+``norm='instance'``, no dropout, ``gan_mode`` lsgan / vanilla / wgangp -- everything the shipped configs select
+(configs/config_px2px.yaml:13-21) and all three objectives of the reference's ``GANLoss``, each one fused HIP pass (``nirgan_lsgan``,
+``nirgan_gan_loss``).  ``cal_gradient_penalty`` is not here (no caller, and it needs a double backward).  Other names the reference
+knows raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from nirgan_hip import functional as HF
+from nirgan_hip import lib as L
 from nirgan_hip.flat import FlatParams
 from nirgan_hip.nets import DiscriminatorEngine, GeneratorEngine
 
@@ -271,18 +274,16 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal'
 
 
 class GANLoss(nn.Module):
-    """networks.py:210-276.  'lsgan' runs the fused HIP loss; the label mask is the reference's
-    0-dim fp32 buffer expanded to the prediction's shape (bit-exact 1.0 / 0.0)."""
+    """networks.py:210-276.  'lsgan' (MSE), 'vanilla' (BCE with logits) and 'wgangp' (-/+ mean) each run one fused HIP loss pass;
+    the label mask is the reference's 0-dim fp32 buffer expanded to the prediction's shape (bit-exact 1.0 / 0.0)."""
 
     def __init__(self, gan_mode, target_real_label=1.0, target_fake_label=0.0):
         super(GANLoss, self).__init__()
         self.register_buffer('real_label', torch.tensor(target_real_label))
         self.register_buffer('fake_label', torch.tensor(target_fake_label))
         self.gan_mode = gan_mode
-        if gan_mode == 'lsgan':
+        if gan_mode in ('lsgan', 'vanilla', 'wgangp'):
             self.loss = None
-        elif gan_mode in ('vanilla', 'wgangp'):
-            raise NotImplementedError('gan mode %s is not on the MI355X path (the shipped configs use lsgan)' % gan_mode)
         else:
             raise NotImplementedError('gan mode %s not implemented' % gan_mode)
         self._label_cache = {}
@@ -304,4 +305,8 @@ class GANLoss(nn.Module):
         return target_tensor.expand_as(prediction)
 
     def __call__(self, prediction, target_is_real):
-        return HF.LsganFn.apply(prediction, self._label_value(target_is_real))
+        if self.gan_mode == 'lsgan':
+            return HF.LsganFn.apply(prediction, self._label_value(target_is_real))
+        # wgangp takes the side from target_is_real alone, as the reference does (networks.py:271-275); the kernel reads it off the value
+        target = self._label_value(target_is_real) if self.gan_mode == 'vanilla' else (1.0 if target_is_real else 0.0)
+        return HF.GanLossFn.apply(prediction, L.GAN_MODES[self.gan_mode], target)

@@ -281,7 +281,7 @@ class Px2Px_PL(_Base):
                 self.netG, self.netD, n_blocks=self.netG.n_blocks, lr=self.opt.lr, beta1=self.opt.beta1,
                 lambda_gan=self.opt.lambda_GAN, lambda_l1=self.opt.lambda_L1, lambda_rs=self.opt.lambda_rs_losses,
                 rs_weights=dict(self.opt.internal_rs_loss_weights), rs_criterion=self.opt.rs_losses_criterium,
-                padding=pad, inject=inject, reducer=reducer, lambda_ssim=self.lambda_ssim)
+                padding=pad, inject=inject, reducer=reducer, lambda_ssim=self.lambda_ssim, gan_mode=self.opt.gan_mode)
         return self._fused
 
     def train_batch(self, batch):

@@ -185,6 +185,27 @@ class LsganFn(torch.autograd.Function):
         return grad * gout, None
 
 
+class GanLossFn(torch.autograd.Function):
+    """GANLoss('vanilla'): BCEWithLogitsLoss(prediction, label.expand_as(prediction)); GANLoss('wgangp'): -prediction.mean() for real,
+    +prediction.mean() for fake (model/networks.py:233-237,258-276).  ``mode`` is lib.GAN_VANILLA / lib.GAN_WGANGP."""
+
+    @staticmethod
+    def forward(ctx, pred, mode: int, target: float):
+        _require_device(pred, "GANLoss")
+        p = pred.detach().contiguous().float()
+        loss = torch.zeros(1, dtype=torch.float32, device=p.device)
+        grad = torch.empty_like(p)
+        st = torch.cuda.current_stream(p.device).cuda_stream if p.device.type == "cuda" else None
+        L.call("nirgan_gan_loss", p.data_ptr(), p.numel(), int(mode), float(target), 1.0, loss.data_ptr(), grad.data_ptr(), st)
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grad,) = ctx.saved_tensors
+        return grad * gout, None, None
+
+
 class PixLossFn(torch.autograd.Function):
     """weights[0]*L1(pred, nir) + sum_i weights[i]*crit(index_i(nir), index_i(pred)); differentiable in pred."""
 

@@ -82,6 +82,9 @@ class TapScatterDesc(C.Structure):
                 ("dq", fp), ("q_hp", i32), ("q_wp", i32), ("q_cs", i32), ("dbias", fp)]
 
 
+GAN_VANILLA, GAN_WGANGP = 1, 2    # include/nirgan_hip.h: NIRGAN_GAN_VANILLA / _WGANGP (nirgan_gan_loss.mode; lsgan has its own entry)
+GAN_MODES = {"vanilla": GAN_VANILLA, "wgangp": GAN_WGANGP}
+
 PIX_LOSS_WS_ELEMS = 8192        # include/nirgan_hip.h: NIRGAN_PIX_LOSS_WS_ELEMS
 
 
@@ -317,6 +320,7 @@ PROTOTYPES = {
     "nirgan_endconv_dgrad": (i32, [C.POINTER(EndConvDesc), fp]),
     "nirgan_endconv_wgrad": (i32, [C.POINTER(EndConvDesc), fp]),
     "nirgan_lsgan": (i32, [fp, i64, f32, f32, fp, fp, fp]),
+    "nirgan_gan_loss": (i32, [fp, i64, i32, f32, f32, fp, fp, fp]),
     "nirgan_pix_loss": (i32, [C.POINTER(PixLossDesc), fp]),
     "nirgan_pixmlp_fwd": (i32, [C.POINTER(PixMlpDesc), fp]),
     "nirgan_pixmlp_train": (i32, [C.POINTER(PixMlpDesc), fp]),

@@ -3,11 +3,14 @@
 One call = one batch of the reference's loop (model/pix2pix.py:165-257 under Lightning's
 two-optimizer schedule, configure_optimizers :485-492):
 
-    optimizer 0 (D): pred = G(rgb);  loss_D = MSE(D(cat(rgb, pred.detach())), 0) + MSE(D(cat(rgb, nir)), 1);
+    optimizer 0 (D): pred = G(rgb);  loss_D = GAN(D(cat(rgb, pred.detach())), fake) + GAN(D(cat(rgb, nir)), real);
                      backward; Adam(D)
-    optimizer 1 (G): D frozen (already updated);  loss_G = l_GAN*MSE(D(cat(rgb, pred)), 1) + l_L1*L1(pred, nir)
+    optimizer 1 (G): D frozen (already updated);  loss_G = l_GAN*GAN(D(cat(rgb, pred)), real) + l_L1*L1(pred, nir)
                      [+ l_rs * sum_i w_i * crit(index_i(nir), index_i(pred))] [+ l_ssim * (1 - mean SSIM_11(pred, nir))];
                      backward; Adam(G)
+
+GAN is the objective of ``gan_mode``: MSE against the label (lsgan, nirgan_lsgan), BCE with logits against the label (vanilla) or
+-/+ the mean (wgangp), the last two through nirgan_gan_loss.
 
 Differences from the reference that do not change results: the generator forward runs once
 (its parameters do not change between the two optimizer passes, so the second forward would
@@ -157,7 +160,7 @@ class Pix2PixTrainer:
     def __init__(self, netG: torch.nn.Module, netD: torch.nn.Module, *, n_blocks: int, lr=2e-4, beta1=0.5,
                  lambda_gan=1.0, lambda_l1=100.0, lambda_rs=0.0, rs_weights: Optional[Dict[str, float]] = None,
                  rs_criterion="l1", padding=0, inject: Optional[dict] = None, reducer=None, precision="fp32",
-                 micro_batches: int = 1, lambda_ssim: float = 0.0):
+                 micro_batches: int = 1, lambda_ssim: float = 0.0, gan_mode: str = "lsgan"):
         self.netG, self.netD = netG, netD
         self.flatG = netG._flat() if hasattr(netG, "_flat") else FlatParams(netG)
         self.flatD = netD._flat() if hasattr(netD, "_flat") else FlatParams(netD)
@@ -167,6 +170,9 @@ class Pix2PixTrainer:
         self.lambda_gan, self.lambda_l1, self.lambda_rs = float(lambda_gan), float(lambda_l1), float(lambda_rs)
         self.lambda_ssim = float(lambda_ssim)
         self.real_label, self.fake_label = 1.0, 0.0      # GANLoss's target_real_label / target_fake_label buffers (networks.py:229-230)
+        if gan_mode != "lsgan" and gan_mode not in L.GAN_MODES:
+            raise NotImplementedError('gan mode %s not implemented' % gan_mode)
+        self.gan_mode = gan_mode
         self.rs_weights = rs_weights or {}
         if rs_criterion not in ("l1", "l2"):
             raise NotImplementedError(f"Criterion '{rs_criterion}' not implemented. 'l1' or 'l2' are supported.")
@@ -223,6 +229,15 @@ class Pix2PixTrainer:
         return ms[0].G.pred if len(ms) == 1 else torch.cat([m.G.pred for m in ms], 0)
 
     # ------------------------------------------------------------------ the two optimizer passes of one micro-batch
+    def _gan_loss(self, be, pred, n, real: bool, weight, loss, grad, st):
+        """One launch of the objective on a patch map: value into its loss slot, gradient into the discriminator's dout."""
+        if self.gan_mode == "lsgan":
+            L.check(be.nirgan_lsgan(pred, n, self.real_label if real else self.fake_label, weight, loss, grad, st), "lsgan")
+        elif self.gan_mode == "vanilla":
+            L.check(be.nirgan_gan_loss(pred, n, L.GAN_VANILLA, self.real_label if real else self.fake_label, weight, loss, grad, st), "gan_loss")
+        else:                                                         # wgangp: the side only (networks.py:271-275)
+            L.check(be.nirgan_gan_loss(pred, n, L.GAN_WGANGP, 1.0 if real else 0.0, weight, loss, grad, st), "gan_loss")
+
     def _d_pass(self, m: _Micro, embeds):
         be, st = L.backend(), m.G.ctx.stream()
         lp = self.losses.data_ptr()
@@ -230,15 +245,15 @@ class Pix2PixTrainer:
         pred = m.G.forward(m.rgb, embeds, version=self.flatG.values_version())              # generator forward (once)
         m.D2.forward(parts=[(m.rgb, 0, 0), (pred, 0, 3), (m.rgb, B, 0), (m.nir, B, 3)], version=self.flatD.values_version())
         out, dout = m.D2.out.data_ptr(), m.D2.dout.data_ptr()
-        L.check(be.nirgan_lsgan(out, npatch, self.fake_label, m.scale, lp, dout, st), "lsgan")
-        L.check(be.nirgan_lsgan(out + npatch * 4, npatch, self.real_label, m.scale, lp + 4, dout + npatch * 4, st), "lsgan")
+        self._gan_loss(be, out, npatch, False, m.scale, lp, dout, st)
+        self._gan_loss(be, out + npatch * 4, npatch, True, m.scale, lp + 4, dout + npatch * 4, st)
         m.D2.backward(None, frozen=False, version=self.flatD.values_version())
 
     def _g_pass(self, m: _Micro):
         be, st = L.backend(), m.G.ctx.stream()
         lp = self.losses.data_ptr()
         m.D1.forward(parts=[(m.rgb, 0, 0), (m.G.pred, 0, 3)], version=self.flatD.values_version())
-        L.check(be.nirgan_lsgan(m.D1.out.data_ptr(), m.n_patch, self.real_label, self.lambda_gan * m.scale, lp + 8, m.D1.dout.data_ptr(), st), "lsgan")
+        self._gan_loss(be, m.D1.out.data_ptr(), m.n_patch, True, self.lambda_gan * m.scale, lp + 8, m.D1.dout.data_ptr(), st)
         m.D1.backward(None, frozen=True, version=self.flatD.values_version(), pred_only=True)
         L.check(be.nirgan_pix_loss(C.byref(m.pix), st), "pix_loss")
         if m.ssim is not None:
