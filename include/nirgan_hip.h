@@ -192,7 +192,10 @@ const char* nirgan_conv_kernel_name(const nirgan_conv_desc* d);
 const char* nirgan_wgrad_kernel_name(const nirgan_wgrad_desc* d);
 const char* nirgan_conv_wgrad_pair_kernel_name(const nirgan_conv_desc* c, const nirgan_wgrad_desc* w);
 
-/* dst[n*dst_row_stride + map[k]] (= | +=) sum_s slabs[s][n][k]  for map[k] >= 0 */
+/* dst[n*dst_row_stride + map[k]] (= | +=) sum_s slabs[s][n][k]  for map[k] >= 0.
+ * K % 4 == 0, 1 <= N <= 65535, slabs 16-byte aligned.  dst_elems clamps: a store whose index n*dst_row_stride + map[k] is >= dst_elems
+ * is DROPPED (no error; nothing at or behind dst + dst_elems is read or written).  The same holds for nirgan_reduce_rows_part and for the
+ * taps = 0 jobs of nirgan_reduce_rows_batch; its taps = T jobs store whole runs and rely on dst_row_stride >= Cin * T instead. */
 int nirgan_reduce_rows(const float* slabs, int nsplit, int N, int K, const int32_t* map,
                        float* dst, int64_t dst_elems, int dst_row_stride, int accumulate, void* stream);
 /* The same over a BAND of the slabs' rows: dst[n*dst_row_stride + map[k]] (= | +=) sum_s slabs[s][row0 + n][k] for n < rows (slabs of
@@ -210,7 +213,10 @@ int nirgan_reduce_rows_part(const float* slabs, int nsplit, int N, int row0, int
  * floats each (same sums, no 4-byte scatter).  total_blocks = the sum; K % 4 == 0, slabs 16-byte aligned. */
 int nirgan_reduce_rows_batch(const int64_t* jobs_device, int njobs, int total_blocks, void* stream);
 
-/* dst[n][k] = map[k] >= 0 ? src[n*src_row_stride + map[k]] : 0   (weight packing) */
+/* dst[n][k] = map[k] >= 0 ? src[n*src_row_stride + map[k]] : 0   (weight packing).
+ * K % 4 == 0, 1 <= N <= 65535, dst 16-byte aligned.  src_elems clamps: a source index n*src_row_stride + map[k] that is >= src_elems
+ * reads as 0 (no error; nothing at or behind src + src_elems is read).  The same holds for nirgan_pack_rows_bf16 and for every job of
+ * nirgan_pack_rows_batch. */
 int nirgan_pack_rows(const float* src, int64_t src_elems, int src_row_stride, const int32_t* map,
                      float* dst, int N, int K, void* stream);
 

@@ -226,19 +226,26 @@ __device__ __forceinline__ void wino6_weight_one(const W6W& p, const long long i
     }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void wino6_weight_kernel(const W6W p) { wino6_weight_one<V>(p, blockIdx.x * 256ll + threadIdx.x); }
-
 // all weight transforms of a step in one launch: 8 x int64 per job {w, U, K, C, flip, first_block, variant, U3 (three bf16 planes of U, or 0)}
-__global__ __launch_bounds__(256) void wino6_weights_batch_kernel(const long long* __restrict__ jobs, int njobs) {
-    int j = 0;
-    for (int i = 1; i < njobs; ++i)
-        if (int(blockIdx.x) >= int(jobs[i * 8 + 5])) j = i;
-    const long long* J = jobs + j * 8;
-    W6W p{reinterpret_cast<const float*>(J[0]), reinterpret_cast<float*>(J[1]), int(J[2]), int(J[3]), int(J[4]), reinterpret_cast<unsigned short*>(J[7])};
-    const long long i = (long long)(int(blockIdx.x) - int(J[5])) * 256 + threadIdx.x;
-    if (J[6] == 4) wino6_weight_one<4>(p, i);
-    else if (J[6] == 6) wino6_weight_one<6>(p, i);
+// jobs == nullptr: the ONE job `one` of variant `one_v` from the kernel arguments (the single launches).  Both forms run this one kernel:
+// which products of G g G^T contract into an FMA is the compiler's choice per kernel, and a kernel of its own for the single launch gave
+// other last bits than the table launch for the same weights.
+__global__ __launch_bounds__(256) void wino6_weights_batch_kernel(const long long* __restrict__ jobs, int njobs, const W6W one, const int one_v) {
+    W6W p = one;
+    long long v = one_v;
+    int first = 0;
+    if (jobs != nullptr) {
+        int j = 0;
+        for (int i = 1; i < njobs; ++i)
+            if (int(blockIdx.x) >= int(jobs[i * 8 + 5])) j = i;
+        const long long* J = jobs + j * 8;
+        p = W6W{reinterpret_cast<const float*>(J[0]), reinterpret_cast<float*>(J[1]), int(J[2]), int(J[3]), int(J[4]), reinterpret_cast<unsigned short*>(J[7])};
+        first = int(J[5]);
+        v = J[6];
+    }
+    const long long i = (long long)(int(blockIdx.x) - first) * 256 + threadIdx.x;
+    if (v == 4) wino6_weight_one<4>(p, i);
+    else if (v == 6) wino6_weight_one<6>(p, i);
     else wino6_weight_one<3>(p, i);
 }
 
@@ -1303,9 +1310,8 @@ static int w6_weights_impl(const float* w, int K, int C, int r, int transpose_fl
     W6W p{w, U, K, C, transpose_flip ? 1 : 0, static_cast<unsigned short*>(U3)};
     const long long n = (long long)K * C;
     const dim3 grid(unsigned((n + 255) / 256));
-    if (r == 3) hipLaunchKernelGGL(wino6_weight_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else if (r == 4) hipLaunchKernelGGL(wino6_weight_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else hipLaunchKernelGGL(wino6_weight_kernel<6>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(wino6_weights_batch_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const long long*>(nullptr), 0, p, r);               // the table kernel on one job: the same bits by construction
     return nirgan_check_launch("wino6_weights");
 }
 
@@ -1316,7 +1322,7 @@ extern "C" int nirgan_wino6_weights(const float* w, int K, int C, int transpose_
 extern "C" int nirgan_wino6_weights_batch(const int64_t* jobs_device, int njobs, int total_blocks, void* stream) {
     NG_REQUIRE(jobs_device && njobs >= 1 && njobs <= 256 && total_blocks >= 1, "wino6_weights_batch: bad arguments");
     hipLaunchKernelGGL(wino6_weights_batch_kernel, dim3(total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const long long*>(jobs_device), njobs);
+                       reinterpret_cast<const long long*>(jobs_device), njobs, W6W{}, 0);
     return nirgan_check_launch("wino6_weights_batch");
 }
 

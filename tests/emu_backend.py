@@ -310,8 +310,18 @@ class EmuBackend:
         rc = self.nirgan_conv_igemm(cref)
         return rc if rc else self.nirgan_wgrad_igemm(wref)
 
+    def _rows_guard(self, who, ptrs, aligned, N, K, kmult=4):
+        """the argument checks of the row kernels' launchers (csrc/igemm_wgrad.hip)"""
+        if not all(ptrs) or not 0 < N <= 65535 or K <= 0 or K % kmult:
+            return self._fail(f"{who}: bad arguments")
+        if int(aligned if not hasattr(aligned, "value") else aligned.value) % 16:
+            return self._fail(f"{who}: pointer must be 16-byte aligned")
+        return 0
+
     def nirgan_reduce_rows(self, slabs, nsplit, N, K, imap, dst, dst_elems, stride, accumulate, stream=None):
         self.calls.append("reduce")
+        if nsplit < 1 or self._rows_guard("reduce_rows", (slabs, imap, dst), slabs, N, K):
+            return self._fail("reduce_rows: bad arguments")
         s = arr(slabs, nsplit * N * K).reshape(nsplit, N, K).sum(0)
         m = arr(imap, K, np.int32)
         o = arr(dst, dst_elems)
@@ -327,6 +337,8 @@ class EmuBackend:
 
     def nirgan_reduce_rows_part(self, slabs, nsplit, N, row0, rows, K, imap, dst, dst_elems, stride, accumulate, stream=None):
         self.calls.append("reduce_part")
+        if nsplit < 1 or self._rows_guard("reduce_rows_part", (slabs, imap, dst), slabs, N, K):
+            return self._fail("reduce_rows_part: bad arguments")
         if row0 < 0 or rows <= 0 or row0 + rows > N:
             return self._fail("reduce_rows_part: rows outside the slab")
         s = arr(slabs, nsplit * N * K).reshape(nsplit, N, K).sum(0)[row0:row0 + rows]
@@ -347,6 +359,8 @@ class EmuBackend:
 
     def nirgan_pack_rows(self, src, src_elems, stride, imap, dst, N, K, stream=None, bf16=False):
         self.calls.append("pack")
+        if self._rows_guard("pack_rows", (src, imap, dst), dst, N, K, 8 if bf16 else 4):
+            return -1
         if bf16:
             tmp = np.zeros((N, K), dtype=np.float32)
             rc = self.nirgan_pack_rows(src, src_elems, stride, imap, tmp.ctypes.data, N, K)
@@ -364,6 +378,8 @@ class EmuBackend:
         return 0
 
     def nirgan_reduce_rows_batch(self, jobs, njobs, total_blocks, stream=None):
+        if not jobs or not 1 <= njobs <= 64 or total_blocks < 1:
+            return self._fail("reduce_rows_batch: bad arguments")
         J = np.ctypeslib.as_array((C.c_int64 * (njobs * 10)).from_address(int(jobs))).reshape(njobs, 10)
         blocks = 0
         for slabs, dst, imap, nsplit, N, K, dst_elems, stride, first, taps in J:
@@ -389,6 +405,8 @@ class EmuBackend:
         return 0
 
     def nirgan_pack_rows_batch(self, jobs, njobs, total_blocks, stream=None):
+        if not jobs or not 1 <= njobs <= 256 or total_blocks < 1:
+            return self._fail("pack_rows_batch: bad arguments")
         J = np.ctypeslib.as_array((C.c_int64 * (njobs * 10)).from_address(int(jobs))).reshape(njobs, 10)
         blocks = 0
         for src, dst, imap, src_elems, N, K, stride, first, w3, w3_plane in J:
@@ -526,6 +544,8 @@ class EmuBackend:
         return self.nirgan_wino6_weights_r(w, K, Cc, r, flip, U, U3=U3)
 
     def nirgan_wino6_weights_batch(self, jobs, njobs, total_blocks, stream=None):
+        if not jobs or not 1 <= njobs <= 256 or total_blocks < 1:
+            return self._fail("wino6_weights_batch: bad arguments")
         J = np.ctypeslib.as_array((C.c_int64 * (njobs * 8)).from_address(int(jobs))).reshape(njobs, 8)
         blocks = 0
         for w, U, K, Cc, flip, first, r, U3 in J:
@@ -761,6 +781,10 @@ class EmuBackend:
     def nirgan_wino6_wgrad_finish_r(self, slabs, nsplit, K, Cc, r, grad, accumulate, stream=None):
         self.calls.append("wino6_fin")
         v = self._r6(r)
+        if v not in self._W6:
+            return self._fail("wino6_wgrad_finish: variant (3, 4 or 6)")
+        if not slabs or not grad or nsplit < 1 or K <= 0 or Cc <= 0:
+            return self._fail("wino6_wgrad_finish: bad arguments")
         r, _, n = self._geo6(v)
         u = arr(slabs, n * n * nsplit * K * Cc).reshape(n, n, nsplit, K, Cc).astype(np.float64).sum(2)
         Gm = self._W6[v][0]
@@ -775,8 +799,12 @@ class EmuBackend:
     def nirgan_wino6_wgrad_finish_batch(self, slabs, grads, n, nsplit, K, Cc, r, accumulate, stream=None):
         if not (1 <= n <= 16):
             return self._fail("wino6_wgrad_finish_batch: 1..16 layers")
+        if self._r6(r) not in self._W6:
+            return self._fail("wino6_wgrad_finish_batch: variant (3, 4 or 6)")
         sp = C.cast(slabs, C.POINTER(C.c_void_p))
         gp = C.cast(grads, C.POINTER(C.c_void_p))
+        if not all(sp[i] and gp[i] for i in range(n)):
+            return self._fail("wino6_wgrad_finish_batch: null pointer in a layer")
         self.calls.append("wino6_fin_batch")
         for i in range(n):
             rc = self.nirgan_wino6_wgrad_finish_r(sp[i], nsplit, K, Cc, r, gp[i], accumulate)
