@@ -480,6 +480,49 @@ int nirgan_pixmlp_train(const nirgan_pixmlp_desc* d, void* stream);
 int64_t nirgan_pixmlp_ws_elems(int B, int H, int W, int hidden);
 
 /* ---------------------------------------------------------------------------------------
+ * The pixel discriminator (1x1 PatchGAN, model/networks.py:587-616 with norm = 'instance'), fused per pixel (csrc/pixdisc.hip):
+ *   z1 = W1 x + b1 (ndf)   h1 = lrelu_0.2(z1)   z2 = W2 h1 (2 ndf)   xh = (z2 - mean_nc) * rstd_nc   out = w3 . lrelu_0.2(xh) + b3
+ * with mean / rstd per sample and channel over H*W (biased variance, eps 1e-5, no affine).  fp32 throughout (fp32 MFMA).
+ * x [B][H][W][4] = cat(rgb, nir | pred), NHWC without halo, 16-byte aligned; out / dout [B][H][W].
+ * `params` / `grads` are the network's flat fp32 ranges (state_dict order net.0.weight, net.0.bias, net.2.weight, net.2.bias,
+ * net.5.weight, net.5.bias, every tensor padded to a multiple of 4 floats: 8772 floats).  net.2.bias feeds the InstanceNorm, which
+ * removes it exactly: the forward does not read it and its gradient is written as exact zeros.
+ *   fwd:  stats[B][2 ndf][2] = (mean of z2 - pivot, rstd), then out.  Two passes over x; z2 is recomputed, never stored.  The pivot of
+ *         (sample, channel) is z2 of the sample's first pixel: it is computed again wherever it is needed and enters the matrix
+ *         products as their starting value, so no rounding at the size of the mean reaches xh.
+ *   bwd:  needs the `stats` the forward of the same x and params left.  Two passes over x and dout:
+ *           mode PARAMS  grads[0..8772) = d (sum dout . out) / d params     (OVERWRITTEN, padding elements and net.2.bias = 0)
+ *           mode INPUT   gx[B][H][W][4] = d (sum dout . out) / d x           (16-byte aligned)
+ *           mode PRED    gx[B][H][W]    = channel 3 of that, bitwise
+ * A 32-pixel tile never straddles two samples; the last tile of a sample is predicated.  Statistics are merged as (count, mean, M2)
+ * with Chan's formula; every reduction runs in index order over records in `ws` (per (sample, chunk of tiles), per sample, per
+ * workgroup), no float atomics, the grid is a function of the shape only (at most 256 workgroups, a CONSTANT of this gfx950-only
+ * library): two runs are bitwise equal.
+ * ndf == 64 only; B, H, W >= 1 with H*W >= 2 (InstanceNorm needs more than one spatial element) and B*H*W < 2^31.  Argument errors
+ * (null pointer, ndf, shape, workspace, mode) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_PIXDISC_PARAMS 0
+#define NIRGAN_PIXDISC_INPUT 1
+#define NIRGAN_PIXDISC_PRED 2
+typedef struct {
+    const float* x;
+    int B, H, W;
+    int ndf;                              /* 64; anything else fails with NIRGAN_ERR_ARG */
+    const float* params;
+    float* stats;                         /* [B][2 ndf][2]: written by fwd, read by bwd */
+    float* out;                           /* fwd */
+    const float* dout;                    /* bwd */
+    float* grads;                         /* bwd, mode PARAMS */
+    float* gx;                            /* bwd, mode INPUT / PRED */
+    int mode;                             /* bwd: NIRGAN_PIXDISC_PARAMS / _INPUT / _PRED */
+    float* ws; int64_t ws_elems;          /* >= the ws_elems query below; not shared between streams; fwd and bwd may share it */
+} nirgan_pixdisc_desc;
+#define NIRGAN_PIXDISC_TILE 32            /* pixels per wave tile */
+int64_t nirgan_pixdisc_ws_elems(int B, int H, int W, int ndf);      /* 0 for a problem the entries refuse */
+int nirgan_pixdisc_fwd(const nirgan_pixdisc_desc* d, void* stream);
+int nirgan_pixdisc_bwd(const nirgan_pixdisc_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam, amsgrad=False, weight_decay=0) on a flat fp32 range.
  * model/pix2pix.py:486-487.  `step` is the 1-based count after increment.
  * ------------------------------------------------------------------------------------- */

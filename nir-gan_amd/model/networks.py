@@ -7,8 +7,8 @@ checkpoints and callers (train.py:48, create_synthetic_dataset.py:21-28) drop in
 are parameter containers: ``forward`` runs the hand-written HIP engines of ``nirgan_hip``
 (there is no torch.nn compute and no CPU fallback).
 
-Supported on this path: ``netG`` resnet_6blocks / resnet_9blocks, ``netD`` basic / n_layers(3),
-``norm='instance'``, no dropout, ``gan_mode`` lsgan / vanilla / wgangp -- everything the shipped configs select
+Supported on this path: ``netG`` resnet_6blocks / resnet_9blocks, ``netD`` basic / n_layers(3) / pixel (ndf 64, fp32 in
+every operand mode), ``norm='instance'``, no dropout, ``gan_mode`` lsgan / vanilla / wgangp -- everything the shipped configs select
 (configs/config_px2px.yaml:13-21) and all three objectives of the reference's ``GANLoss``, each one fused HIP pass (``nirgan_lsgan``,
 ``nirgan_gan_loss``).  ``cal_gradient_penalty`` is not here (no caller, and it needs a double backward).  Other names the reference
 knows raise NotImplementedError.
@@ -25,7 +25,7 @@ from torch.nn import init
 from nirgan_hip import functional as HF
 from nirgan_hip import lib as L
 from nirgan_hip.flat import FlatParams
-from nirgan_hip.nets import DiscriminatorEngine, GeneratorEngine
+from nirgan_hip.nets import DiscriminatorEngine, GeneratorEngine, PixelDiscriminatorEngine
 
 
 # --------------------------------------------------------------------------------------------
@@ -245,6 +245,35 @@ class NLayerDiscriminator(_HipNet):
         return HF.DiscriminatorFn.apply(self, torch.is_grad_enabled(), input, *self.parameters())
 
 
+class PixelDiscriminator(_HipNet):
+    """1x1 PatchGAN (pixelGAN, networks.py:587-616) on the fused per-pixel kernels (csrc/pixdisc.hip): Conv1x1(4, 64), LeakyReLU,
+    Conv1x1(64, 128), InstanceNorm, LeakyReLU, Conv1x1(128, 1).  The attribute is the reference's ``net``, so the state_dict keys are
+    net.0 / net.2 / net.5 (.weight, .bias); net.2.bias feeds the InstanceNorm and has gradient exactly 0."""
+
+    engine_class = PixelDiscriminatorEngine
+
+    def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d):
+        super().__init__()
+        if not _is_instance(norm_layer):
+            raise NotImplementedError('only norm="instance" runs on the MI355X path (the shipped configs use it)')
+        if input_nc != 4 or ndf != 64:
+            raise NotImplementedError('the MI355X path covers the pixel discriminator with ndf=64 on cat(rgb, nir)')
+        use_bias = True
+        self.net = nn.Sequential(
+            Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0), nn.LeakyReLU(0.2, True),
+            Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias), norm_layer(ndf * 2), nn.LeakyReLU(0.2, True),
+            Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias))
+
+    def _make_engine(self, key):
+        B, H, W, need_bwd = key
+        f = self._flat()
+        return PixelDiscriminatorEngine(f.param_views(), f.grad_views(), B, H, W, need_backward=need_bwd,
+                                        precision=getattr(self, "precision", "fp32"))
+
+    def forward(self, input):
+        return HF.DiscriminatorFn.apply(self, torch.is_grad_enabled(), input, *self.parameters())
+
+
 def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal', init_gain=0.02, gpu_ids=[]):
     """networks.py:120-160."""
     norm_layer = get_norm_layer(norm_type=norm)
@@ -266,8 +295,8 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal'
         net = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer)
     elif netD == 'n_layers':
         net = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer)
-    elif netD == 'pixel':
-        raise NotImplementedError('Discriminator model name [pixel] is not on the MI355X path (no shipped config selects it)')
+    elif netD == 'pixel':     # n_layers_D is ignored, as in the reference
+        net = PixelDiscriminator(input_nc, ndf, norm_layer=norm_layer)
     else:
         raise NotImplementedError('Discriminator model name [%s] is not recognized' % netD)
     return init_net(net, init_type, init_gain, gpu_ids)

@@ -104,6 +104,15 @@ class PixMlpDesc(C.Structure):
                 ("params", fp), ("grads", fp), ("pred", fp), ("loss_out", fp), ("ws", fp), ("ws_elems", i64)]
 
 
+PIXDISC_TILE = 32               # include/nirgan_hip.h: NIRGAN_PIXDISC_TILE
+PIXDISC_PARAMS, PIXDISC_INPUT, PIXDISC_PRED = 0, 1, 2     # include/nirgan_hip.h: NIRGAN_PIXDISC_* (nirgan_pixdisc_desc.mode)
+
+
+class PixDiscDesc(C.Structure):
+    _fields_ = [("x", fp), ("B", i32), ("H", i32), ("W", i32), ("ndf", i32), ("params", fp), ("stats", fp), ("out", fp), ("dout", fp),
+                ("grads", fp), ("gx", fp), ("mode", i32), ("ws", fp), ("ws_elems", i64)]
+
+
 class InjectFwdDesc(C.Structure):
     _fields_ = [("z", fp), ("e", fp), ("scale", fp), ("style", i32), ("B", i32), ("H", i32), ("W", i32), ("C", i32),
                 ("out", fp), ("o_hp", i32), ("o_wp", i32), ("o_pad", i32)]
@@ -325,6 +334,9 @@ PROTOTYPES = {
     "nirgan_pixmlp_fwd": (i32, [C.POINTER(PixMlpDesc), fp]),
     "nirgan_pixmlp_train": (i32, [C.POINTER(PixMlpDesc), fp]),
     "nirgan_pixmlp_ws_elems": (i64, [i32, i32, i32, i32]),
+    "nirgan_pixdisc_ws_elems": (i64, [i32, i32, i32, i32]),
+    "nirgan_pixdisc_fwd": (i32, [C.POINTER(PixDiscDesc), fp]),
+    "nirgan_pixdisc_bwd": (i32, [C.POINTER(PixDiscDesc), fp]),
     "nirgan_adam": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, f32, i32, fp]),
     "nirgan_bilinear_fwd": (i32, [fp, i32, i32, i32, fp, i32, i32, fp]),
     "nirgan_bilinear_bwd": (i32, [fp, i32, i32, i32, fp, i32, i32, fp]),

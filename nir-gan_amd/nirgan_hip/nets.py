@@ -1,4 +1,4 @@
-"""Network-level engines: the ResNet generator (plain and SatCLIP-inject) and the PatchGAN.
+"""Network-level engines: the ResNet generator (plain and SatCLIP-inject), the PatchGAN and the pixel discriminator.
 
 Each engine is bound to one parameter set (device tensors in the reference layouts, keyed by
 the reference's state_dict names) and one shape.  ``forward`` consumes / produces NCHW tensors
@@ -393,6 +393,103 @@ class DiscriminatorEngine(_Engine):
         """frozen=False: parameter gradients.  frozen=True: gradient wrt the input ([B][H][W][4]), or wrt its
         channel 3 only ([B][H][W]) when pred_only."""
         self.refresh_weights(version, backward=True)
+        if dout is not None:
+            self.dout.copy_(dout)
+        if not frozen:
+            self.bwd.run()
+            return None
+        if pred_only:
+            self.bwd_pred.run()
+            return self.gpred
+        self.bwd_frozen.run()
+        return self.gx4.t
+
+
+class PixelDiscriminatorEngine:
+    """PixelDiscriminator(input_nc=4, ndf=64, InstanceNorm): the 1x1 PatchGAN (model/networks.py:587-616) on the fused per-pixel
+    kernels of csrc/pixdisc.hip, with the interface DiscriminatorEngine gives the trainer and the autograd bridge.
+
+    ``precision`` ('fp32', 'bf16', 'bf16x3') is accepted for symmetry with the other engines; this network runs fp32 (fp32 MFMA) in
+    every mode: its three contractions are 4, 64 and 128 deep and bound by the 20 bytes per pixel, not by the matrix pipe.
+    The whole gradient (8772 floats) is final only after the merge launch: there is no ``bwd_tail`` / ``bwd_mid`` bucket."""
+
+    FLAT_ELEMS = 8772
+
+    def __init__(self, params: Dict[str, torch.Tensor], grads: Optional[Dict[str, torch.Tensor]], B: int, H: int, W: int,
+                 need_backward: bool = True, precision="fp32"):
+        w1 = params["net.0.weight"]
+        self.ctx = ctx = Ctx(w1.device, precision)
+        self.params, self.grads, self.B, self.H, self.W = params, grads, B, H, W
+        ndf, in_nc = w1.shape[0], w1.shape[1]
+        if in_nc != 4 or ndf != 64:
+            raise NotImplementedError("the pixel discriminator of the MI355X path is built for cat(rgb, nir) = 4 channels and ndf = 64")
+        if H * W < 2:       # what torch's InstanceNorm2d answers (torch/nn/functional.py::_verify_spatial_size)
+            raise ValueError(f"Expected more than 1 spatial element when training, got input size {torch.Size([B, 2 * ndf, H, W])}")
+        base = w1.data_ptr()
+        assert params["net.5.bias"].data_ptr() - base == 4 * (self.FLAT_ELEMS - 4), "parameters are not one flat range (nirgan_hip/flat.py)"
+        n_ws = int(L.backend().nirgan_pixdisc_ws_elems(B, H, W, ndf))
+        if n_ws <= 0:
+            raise ValueError(f"pixel discriminator: {B} x {H} x {W} is not a shape the kernels take (B*H*W < 2^31)")
+        self.x_in = ctx.zeros(B, 4, H, W)
+        self.x4 = Halo(ctx, B, H, W, 4, 0)
+        self.stats = ctx.zeros(B, 2 * ndf, 2)
+        self.out = ctx.zeros(B, 1, H, W)
+        self.ws = ctx.zeros(n_ws)
+
+        def desc(mode=L.PIXDISC_PARAMS):
+            d = L.PixDiscDesc()
+            d.x, d.B, d.H, d.W, d.ndf = self.x4.ptr, B, H, W, ndf
+            d.params, d.stats, d.out = base, self.stats.data_ptr(), self.out.data_ptr()
+            d.mode, d.ws, d.ws_elems = mode, self.ws.data_ptr(), n_ws
+            ctx.keep.append(d)
+            return d
+        self.fwd = Plan(ctx)
+        self.fwd.add("nirgan_pixdisc_fwd", C.byref(desc()))
+        self.in_plan = Plan(ctx)
+        self.in_plan.add("nirgan_nchw_to_halo", self.x_in.data_ptr(), B, 4, H, W, self.x4.ptr, 4, 0, 0, 0, L.BORDER_KEEP)
+        self._part_plans: dict = {}
+        if need_backward:
+            assert grads is not None
+            gbase = grads["net.0.weight"].data_ptr()
+            assert grads["net.5.bias"].data_ptr() - gbase == 4 * (self.FLAT_ELEMS - 4), "gradients are not one flat range"
+            self.dout = ctx.zeros(B, 1, H, W)
+            self.gx4 = Halo(ctx, B, H, W, 4, 0)
+            self.gpred = ctx.zeros(B, H, W)
+            self.bwd, self.bwd_frozen, self.bwd_pred = Plan(ctx), Plan(ctx), Plan(ctx)
+            for plan, mode, gx in ((self.bwd, L.PIXDISC_PARAMS, None), (self.bwd_frozen, L.PIXDISC_INPUT, self.gx4.ptr),
+                                   (self.bwd_pred, L.PIXDISC_PRED, self.gpred.data_ptr())):
+                d = desc(mode)
+                d.dout, d.gx = self.dout.data_ptr(), gx
+                d.grads = gbase if mode == L.PIXDISC_PARAMS else None
+                plan.add("nirgan_pixdisc_bwd", C.byref(d))
+
+    def input_plan(self, parts) -> Plan:
+        """parts: list of (NCHW tensor [nb, Cs, H, W], b0, c0) written straight into the [B][H][W][4] input
+        (the torch.cat of model/pix2pix.py:197,202,216 never materialises)."""
+        key = tuple((t.data_ptr(), t.shape[0], t.shape[1], b0, c0) for t, b0, c0 in parts)
+        if key not in self._part_plans:
+            pl = Plan(self.ctx)
+            for t, b0, c0 in parts:
+                nb, cs = t.shape[0], t.shape[1]
+                assert t.is_contiguous() and t.shape[2] == self.H and t.shape[3] == self.W and b0 + nb <= self.B
+                dst = self.x4.ptr + b0 * self.H * self.W * 4 * 4
+                pl.add("nirgan_nchw_to_halo", t.data_ptr(), nb, cs, self.H, self.W, dst, 4, c0, 0, 0, L.BORDER_KEEP)
+            self._part_plans[key] = pl
+        return self._part_plans[key]
+
+    def forward(self, x: Optional[torch.Tensor] = None, parts=None, version: int = 0) -> torch.Tensor:
+        """``version`` is accepted and unused: the kernels read the parameters in place, there is nothing to re-pack."""
+        if parts is not None:
+            self.input_plan(parts).run()
+        else:
+            self.x_in.copy_(x)
+            self.in_plan.run()
+        self.fwd.run()
+        return self.out
+
+    def backward(self, dout: Optional[torch.Tensor], frozen: bool = False, version: int = 0, pred_only: bool = False) -> Optional[torch.Tensor]:
+        """frozen=False: parameter gradients (the flat gradient range is overwritten).  frozen=True: gradient wrt the input
+        ([B][H][W][4]), or wrt its channel 3 only ([B][H][W]) when pred_only.  Needs the statistics of this engine's last forward."""
         if dout is not None:
             self.dout.copy_(dout)
         if not frozen:

@@ -42,8 +42,9 @@ class _Micro:
         self.lo, self.hi, self.B, self.scale = lo, hi, B, scale
         gp, dp = tr.flatG.param_views(), tr.flatD.param_views()
         self.G = GeneratorEngine(gp, gradG, tr.n_blocks, B, H, W, data_pad=tr.padding, inject=tr.inject, precision=tr.precision)
-        self.D2 = DiscriminatorEngine(dp, gradD, 2 * B, H, W, precision=tr.precision)
-        self.D1 = DiscriminatorEngine(dp, gradD, B, H, W, precision=tr.precision)
+        d_engine = getattr(tr.netD, "engine_class", DiscriminatorEngine)       # netD 'pixel': nets.PixelDiscriminatorEngine
+        self.D2 = d_engine(dp, gradD, 2 * B, H, W, precision=tr.precision)
+        self.D1 = d_engine(dp, gradD, B, H, W, precision=tr.precision)
         self.rgb = torch.zeros(B, 3, H, W, dtype=torch.float32, device=dev)
         self.nir = torch.zeros(B, 1, H, W, dtype=torch.float32, device=dev)
         self.n_patch = self.D1.B * self.D1.out[0].numel()
@@ -102,11 +103,15 @@ class _ShapeState:
         # data parallel, single part: three gradient buckets per network -- the tail of the flat gradient goes to RCCL from inside
         # the backward plan, as soon as the launches that complete it are on the stream (parallel.GradReducer.begin), the middle in
         # front of the first layer's backward; only the first layer's gradient (the head) follows after the plan.  With micro-batches the side parts are added after the plans: one bucket, after the join.
+        # The decision is per network: an engine without a ``bwd_tail`` (the pixel discriminator: 35 KB, final only after its merge
+        # launch) goes as one blocking all-reduce while the generator keeps its buckets.
         self.bucketed = tr.reducer is not None and n == 1 and OPT.dp_buckets
+        self.bucketedD = self.bucketed and hasattr(self.micros[0].D2, "bwd_tail")
         self.headD = self.headG = None
         if self.bucketed:
             m = self.micros[0]
-            self.headD = self._hook_tail(tr, m.D2, tr.flatD)
+            if self.bucketedD:
+                self.headD = self._hook_tail(tr, m.D2, tr.flatD)
             self.headG = self._hook_tail(tr, m.G, tr.flatG)
 
     @staticmethod
@@ -275,10 +280,11 @@ class Pix2PixTrainer:
             L.call("nirgan_axpy", flat.grad.data_ptr(), buf.data_ptr(), flat.total, 1.0, st)
 
     def _reduce(self, state: _ShapeState, flat: FlatParams, head):
-        """Average the network's gradient over the ranks before its Adam step (DDP's all-reduce during backward)."""
+        """Average the network's gradient over the ranks before its Adam step (DDP's all-reduce during backward).  ``head``: what is
+        left of a bucketed network's gradient after its backward plan; None for a network that goes as one all-reduce."""
         if self.reducer is None:
             return
-        if state.bucketed:
+        if head is not None:
             for part in head:                 # the tail bucket has been in flight since the middle of the backward plan
                 self.reducer.begin(part)
             self.reducer.finish()
