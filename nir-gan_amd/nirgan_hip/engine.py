@@ -56,6 +56,17 @@ class Ctx:
         self.zero_page = torch.zeros(64, dtype=torch.float32, device=self.device)
         self.keep: list = []
         self.bytes = 0
+        # lists while a network's backward plan collects its weight-gradient finishes (the slab sums: emit_wgrad -> emit_deferred_reduce_rows;
+        # the Winograd inverse transforms: emit_wino6_backward -> emit_w6_deferred_finishes), None otherwise: every layer finishes its own
+        self.rr_deferred = self.w6_deferred = None
+        self.pools: dict = {}
+
+    def pool(self, name, make=None):
+        """The context's shared workspace of that name, created on first use: ONE per name and context (the launches of a context run
+        serially; the engines of two micro-batches have a context each).  A SplitPool unless `make` builds something else."""
+        if name not in self.pools:
+            self.pools[name] = make() if make is not None else SplitPool(self)
+        return self.pools[name]
 
     def zeros(self, *shape) -> torch.Tensor:
         t = torch.zeros(*shape, dtype=torch.float32, device=self.device)
@@ -103,6 +114,8 @@ class Halo:
         # set by drop_dead_fp32_stores: the storage decision of this buffer (fp32 + twin, twin only, fp32 only) is taken from the readers
         # seen so far, so a launch emitted afterwards must not register as a new reader (it would read a tensor nobody maintains)
         self.finalised = False
+        self.w6_out_desc = None        # set by the ConvIN whose Winograd data gradient writes this buffer; the ConvIN that consumes the gradient may arm its fused output transform
+        self.conv_out_descs = None     # set by the ConvIN whose direct-tile data gradient writes this buffer; the consumer may arm the epilogues' instance-norm first pass
 
     @property
     def ptr(self):
@@ -360,7 +373,7 @@ def emit_conv(plan: Plan, ctx: Ctx, inp: Halo, taps: G.Taps, w: torch.Tensor, bi
     d.w_bf16 = 1 if w.dtype == torch.bfloat16 else 0
     if d.w_bf16 and taps.run % 8:
         raise ValueError(f"bf16-stored weights need run % 8 == 0 (run={taps.run})")
-    d.out_bf16 = 1 if getattr(out, "is16", False) else 0
+    d.out_bf16 = 1 if out.is16 else 0
     d.out, d.out_elems = (out.ptr_any() if d.out_bf16 else out.ptr), out.elems
     if d.out_bf16:
         allow_split = False          # a bf16 output is stored by the tile's own epilogue (no split-K workspace pass)
@@ -390,9 +403,7 @@ def emit_conv(plan: Plan, ctx: Ctx, inp: Halo, taps: G.Taps, w: torch.Tensor, bi
         tiles = -(-M // 128) * (-(-N // 128) if N > 64 else 1)
         ks = choose_ksplit(tiles, taps.n * (-(-taps.run // 32))) if (allow_split and N % 4 == 0) else 1
         if ks > 1:
-            if not hasattr(ctx, "split_pool"):
-                ctx.split_pool = SplitPool(ctx)
-            ws = ctx.split_pool.get(ks * M * N)
+            ws = ctx.pool("split").get(ks * M * N)
             d.ksplit, d.split_ws, d.split_ws_elems = ks, ws.data_ptr(), ws.numel()
         plan.add("nirgan_conv_igemm", C.byref(d))
     return d
@@ -431,7 +442,7 @@ def emit_wgrad(plan: Plan, ctx: Ctx, p: Halo, q: Halo, taps: G.Taps, spec: G.Pac
     # deferred slab sums (ctx.rr_deferred is a list while a network's backward plan is being built): the layer keeps its own slabs and all
     # of them are summed by ONE launch at the plan's next flush point (emit_deferred_reduce_rows: where a data-parallel bucket is final,
     # and at the end of the plan)
-    deferred = getattr(ctx, "rr_deferred", None)
+    deferred = ctx.rr_deferred
     slabs = ctx.zeros(need) if deferred is not None else (slabs_pool.get(need) if slabs_pool is not None else ctx.zeros(need))
     ctx.keep.append(slabs)
     d = L.WgradDesc()
@@ -469,7 +480,7 @@ def emit_deferred_reduce_rows(plan: Plan, ctx: Ctx, last: bool = True):
     """ONE nirgan_reduce_rows_batch for the weight gradients collected in ctx.rr_deferred since the last flush (up to 64 per launch): a
     single layer's slab sum is 12-14 us of launch latency for up to 31 MB; a dozen in one grid run at the memory rate.  `last` ends the
     collection (the end of the plan); otherwise the list stays open for the layers behind this flush point."""
-    if getattr(ctx, "rr_deferred", None) is None:
+    if ctx.rr_deferred is None:
         return
     items = ctx.rr_deferred
     ctx.rr_deferred = None if last else []
@@ -503,6 +514,8 @@ def wino_dgrad_applicable(ctx: Ctx, k, s, dgrad_out: Halo, cout, cin) -> bool:
 
 class _FullExtent:
     """A halo'd buffer seen as the dense [B][hp][wp][C] tensor it is in memory (the data gradient covers the padded extent)."""
+
+    is16 = False
 
     def __init__(self, h: Halo):
         self.B, self.hp, self.wp, self.C, self.ptr = h.B, h.hp, h.wp, h.C, h.ptr
@@ -556,15 +569,12 @@ def emit_wino6(plan: Optional[Plan], pack: Plan, ctx: Ctx, x: Halo, weight: torc
         U = ctx.zeros(NP * cout * cin)
         ctx.keep.append(U)
         pack.add("nirgan_wino6_weights_r", weight.data_ptr(), cout, cin, v, 1 if flip else 0, U.data_ptr())
-    for name in ("wino6_pool_v", "wino6_pool_m"):
-        if not hasattr(ctx, name):
-            setattr(ctx, name, SplitPool(ctx))          # one layer at a time (launches run serially)
     if own_V:                                          # kept for the layer's weight gradient (same x): 2.25 x the input bytes, resident
         V = ctx.zeros(NP * T * cin)
         ctx.keep.append(V)
     else:
-        V = ctx.wino6_pool_v.get(NP * T * cin)
-    M = ctx.wino6_pool_m.get(NP * T * cout)
+        V = ctx.pool("wino6_v").get(NP * T * cin)          # one layer at a time (launches run serially)
+    M = ctx.pool("wino6_m").get(NP * T * cout)
     d = L.Wino6Desc()
     d.r = v
     d.x, d.x_hp, d.x_wp = x.ptr, x.hp, x.wp
@@ -602,19 +612,15 @@ def emit_wino6_backward(plan: Plan, ctx: Ctx, dy: Halo, inp: Halo, grad: torch.T
     assert dgrad.r == v
     T = _w6_tiles(B, OH, OW, v)
     NP = _w6_geo(v)[1]
-    for name in ("wino6_pool_x", "wino6_pool_y", "wino6_slabs"):
-        if not hasattr(ctx, name):
-            setattr(ctx, name, SplitPool(ctx))
     # (round 3, measured: the weight gradient on an auxiliary stream as a one-workgroup-per-CU launch under the HBM-bound chain that
     # follows the data gradient overlaps zero-sum -- profiles/r03_side_stream_1wg_per_cu_experiment.txt; the option is gone)
-    Yt = ctx.wino6_pool_y.get(NP * T * cout)
-    if V_fwd is not None:
-        slabs_pool = ctx.wino6_slabs
+    Yt = ctx.pool("wino6_y").get(NP * T * cout)
     vin = None
     if V_fwd is not None:
+        slabs_pool = ctx.pool("wino6_slabs")
         V_ptr, V_elems = V_fwd.V, V_fwd.V_elems
     else:
-        V = ctx.wino6_pool_x.get(NP * T * cin)
+        V = ctx.pool("wino6_x").get(NP * T * cin)
         vin = L.Wino6Desc()
         vin.r = v
         vin.x, vin.x_hp, vin.x_wp, vin.B, vin.H, vin.W, vin.C, vin.K = inp.ptr, inp.hp, inp.wp, B, OH, OW, cin, cout
@@ -638,7 +644,7 @@ def emit_wino6_backward(plan: Plan, ctx: Ctx, dy: Halo, inp: Halo, grad: torch.T
         nsplit, rows = G.wgrad_split(T, units, max(G.CUS, units), 32)
     # deferred finish (ctx.w6_deferred is a list while a network collects the layers of one trunk): the layer keeps its own slabs and the
     # inverse transforms of all of them run as ONE launch behind the trunk (emit_w6_deferred_finishes)
-    deferred = getattr(ctx, "w6_deferred", None) if persistent else None
+    deferred = ctx.w6_deferred if persistent else None
     slabs = ctx.zeros(NP * nsplit * cout * cin) if deferred is not None else slabs_pool.get(NP * nsplit * cout * cin)
     d = L.WgradDesc()
     d.p, d.p_elems, d.p_hp, d.p_wp, d.p_cs, d.p_oh, d.p_ow = Yt.data_ptr(), NP * T * cout, 1, T, cout, 0, 0
@@ -676,7 +682,7 @@ def emit_wino6_backward(plan: Plan, ctx: Ctx, dy: Halo, inp: Halo, grad: torch.T
 def emit_w6_deferred_finishes(plan: Plan, ctx: Ctx):
     """One nirgan_wino6_wgrad_finish_batch per geometry for the layers collected in ctx.w6_deferred (at most 16 per launch): a single
     layer's inverse transform is 17 us of launch latency for 33 MB of slabs, twelve in one grid run at the memory rate."""
-    items, ctx.w6_deferred = (getattr(ctx, "w6_deferred", None) or []), None
+    items, ctx.w6_deferred = (ctx.w6_deferred or []), None
     groups = {}
     for slabs, nsplit, K, Cc, v, grad, acc in items:
         groups.setdefault((nsplit, K, Cc, v, acc), []).append((slabs, grad))
@@ -707,9 +713,7 @@ def attach_conv_stats(ctx: Ctx, descs: list, bias) -> Optional[tuple]:
     B, N = descs[0].B, channels_of(descs[0])
     recs = [d.OH * d.OW // 64 * max(1, d.out_span) for d in descs]       # (a paired problem leaves two records per 64 rows)
     total = sum(recs)
-    if not hasattr(ctx, "conv_pool_stats"):
-        ctx.conv_pool_stats = SplitPool(ctx)
-    ws = ctx.conv_pool_stats.get(B * total * 4 * N)
+    ws = ctx.pool("conv_stats").get(B * total * 4 * N)
     first = 0
     for d, n in zip(descs, recs):
         d.stats_ws, d.stats_ws_elems, d.stats_chunk0, d.stats_chunks = ws.data_ptr(), ws.numel(), first, total
@@ -757,7 +761,7 @@ def want_phase_pairs(ctx: Ctx, phases: list, run: int, N: int, out) -> bool:
     3 x 3 kernel) runs as two paired problems of 128 columns on it (nirgan_conv_desc.out_span = 2, geometry.pair_row_phases): measured
     412 / 349 us -> see DESIGN 3.1 for ConvTranspose2d(128, 64, 3, s2) at bs 16 / the data gradient of Conv2d(64, 128, 3, s2)."""
     return (ctx.precision == 0 and OPT.split3 and OPT.pair_phases and N == 64 and run % 32 == 0 and out.C == N and out.C % 4 == 0
-            and not getattr(out, "is16", False) and len(phases) == 4 and min(len(ph.dh) for ph in phases) * run < 512)
+            and not out.is16 and len(phases) == 4 and min(len(ph.dh) for ph in phases) * run < 512)
 
 
 def emit_phase_pairs(eng, pack: Plan, ctx: Ctx, inp: Halo, phases: list, spec_fn, weight, bias, out: Halo, *, N, in_off, out_off):
@@ -956,6 +960,18 @@ class _Scratch:
 # ---------------------------------------------------------------------------------------------
 # layer bundles: each keeps its buffers and emits forward / backward ops
 # ---------------------------------------------------------------------------------------------
+class LayerHost:
+    """What ConvIN / TapPlaneConv ask of the engine they belong to (nets._Engine derives from it; a kernel test builds one on its context)."""
+
+    def __init__(self, ctx: Ctx, keep_wino_V: bool = False):
+        self.ctx = ctx
+        self.weights, self.slabs, self.scratch = Weights(ctx), SlabPool(ctx), _Scratch(ctx)
+        self.twinned: list = []              # every layer's `out` and `dy`: see drop_dead_fp32_stores
+        self.keep_wino_V = keep_wino_V       # a Winograd forward keeps V = B^T x B resident for the layer's transform-domain weight gradient
+        self.bwd_tail = self.bwd_mid = None  # data parallel: (op index in bwd, first key, last key) of a gradient bucket; None = no bucket
+        self._packs_fused = False
+
+
 class ConvIN:
     """conv (Conv2d / ConvTranspose2d / row-packed first conv) -> [InstanceNorm] -> act -> halo'd output.
 
@@ -985,43 +1001,66 @@ class ConvIN:
                and self.OH * self.OW >= min(OPT.epilogue_min_pixels, OPT.epilogue_min_pixels_bf16) and one_pass_tiles(B * phase_px, cout))
         self.y = Halo(ctx, B, self.OH, self.OW, cout, 0, bf16=y16)
         self.out = Halo(ctx, B, self.OH, self.OW, cout, out_pad, twin=True)
-        eng.__dict__.setdefault("twinned", []).append(self.out)          # see drop_dead_fp32_stores
+        eng.twinned.append(self.out)
         self.out_border = out_border
         self.stats = (ctx.zeros(B, cout), ctx.zeros(B, cout)) if norm else None
         eng.scratch.want(B, self.OH, self.OW, cout)
         self.keep_z = keep_z   # inject: `out` holds z (no act); the modulation produces the activated tensor
+        self.producer, self.defer_apply = None, False       # fold_producer_apply: the consumer's link / the producer's "statistics only"
+        self.wino6, self.wino_fwd, self.wino_fwd_keeps_V = False, None, False       # emit_fwd: Winograd layer, its descriptor, V resident
 
-    # ---- forward
+    def fold_producer_apply(self, producer: "ConvIN"):
+        """`producer.out` has this layer as its ONE reader: InstanceNorm + activation + reflect pad of the producer move into this layer's
+        Winograd input transform (emit_fwd) and the producer leaves its statistics only."""
+        producer.defer_apply, self.producer = True, producer
+
+    # ---- forward: each _emit_fwd_* returns `pre` = (chunks per sample, shift, workspace) when the convolution's last kernel leaves the
+    # instance norm's partial sums, else None
     def emit_fwd(self, plan: Plan, pack: Plan):
         eng, ctx, inp = self.eng, self.eng.ctx, self.inp
+        if self.kind == "conv" and wino_applicable(ctx, inp, self.k, self.s, self.p, self.cout, self.OH, self.OW):
+            pre = self._emit_fwd_wino6(plan, pack)
+        elif self.kind in ("conv", "rowpacked"):
+            pre = self._emit_fwd_direct(plan, pack)
+        else:  # convT: 4 sub-pixel phases over the zero-halo-1 input, one launch
+            descs = self._phase_descs(pack, inp, self.y, G.convT_fwd_phases(inp.H, inp.W, self.k, self.p),
+                                      lambda hw: G.convT_fwd_pack(inp.C, self.cout, self.k, hw), self.bias, run=inp.C, N=self.cout,
+                                      in_off=inp.pad - 1, out_off=0)
+            pre = self._conv_stats(descs)
+            emit_conv_group(plan, ctx, descs)
+        emit_in_fwd(plan, ctx, self.y, self.out, norm=self.norm, act=(L.ACT_NONE if self.keep_z else self.act),
+                    residual=self.residual, border=self.out_border, stats=self.stats, ws=(pre[2] if pre is not None else eng.scratch.get()),
+                    stats_only=self.defer_apply, pre_stats=(pre[:2] if pre is not None else None))
+
+    def _emit_fwd_wino6(self, plan: Plan, pack: Plan):
+        eng, ctx, inp, k = self.eng, self.eng.ctx, self.inp, self.k
+        keep = bool(eng.keep_wino_V)     # V = B^T x B stays resident for the layer's transform-domain weight gradient
+        prod = self.producer
+        xn = (prod.y, prod.stats, prod.act) if prod is not None and prod.defer_apply else None
+        self.wino6 = True
+        pre = sws = None
+        if self.norm and OPT.epilogue_stats:
+            # instance-norm statistics from the output transform's own pass (one chunk of partial sums per tile)
+            T = _w6_tiles(inp.B, self.OH, self.OW, wino6_variant(k))
+            sws = ctx.pool("wino6_stats").get(T * 4 * self.cout)
+            pre = (T // inp.B, self.bias, sws)
+        self.wino_fwd = emit_wino6(plan, pack, ctx, inp, self.weight, self.bias, self.y, H=self.OH, W=self.OW, cin=inp.C,
+                                   cout=self.cout, own_V=keep, x_norm=xn, r=k, stats_ws=sws)
+        self.wino_fwd_keeps_V = keep
+        return pre
+
+    def _direct_problem(self):
+        """(taps, pack spec) of the forward problem of a 'conv' / 'rowpacked' layer on the direct tiles -- and of its weight gradient."""
+        k, cs = self.k, self.inp.C
+        if self.kind == "conv":
+            return G.conv_fwd_taps(k, cs), G.conv_fwd_pack(self.cout, cs, k)
+        return G.conv_rowpacked_taps(k, cs), G.conv_rowpacked_pack(self.cout, self.cin, k, cs)
+
+    def _emit_fwd_direct(self, plan: Plan, pack: Plan):
+        eng, ctx, inp = self.eng, self.eng.ctx, self.inp
         k, s, p = self.k, self.s, self.p
-        pre = None          # (chunks per sample, shift, workspace) when the convolution's last kernel leaves the instance norm's partial sums
-        if self.kind == "conv" and wino_applicable(ctx, inp, k, s, p, self.cout, self.OH, self.OW):
-            keep = bool(getattr(eng, "need_backward", False))     # V = B^T x B stays resident for the layer's transform-domain weight gradient
-            prod = getattr(self, "producer", None)
-            xn = (prod.y, prod.stats, prod.act) if prod is not None and getattr(prod, "defer_apply", False) else None
-            self.wino6 = True
-            sws = None
-            if self.norm and OPT.epilogue_stats:
-                # instance-norm statistics from the output transform's own pass (one chunk of partial sums per tile)
-                T = _w6_tiles(inp.B, self.OH, self.OW, wino6_variant(k))
-                if not hasattr(ctx, "wino6_pool_stats"):
-                    ctx.wino6_pool_stats = SplitPool(ctx)
-                sws = ctx.wino6_pool_stats.get(T * 4 * self.cout)
-                pre = (T // inp.B, self.bias, sws)
-            self.wino_fwd = emit_wino6(plan, pack, ctx, inp, self.weight, self.bias, self.y, H=self.OH, W=self.OW, cin=inp.C,
-                                       cout=self.cout, own_V=keep, x_norm=xn, r=k, stats_ws=sws)
-            self.wino_fwd_keeps_V = keep
-        elif self.kind == "conv":
-            taps = G.conv_fwd_taps(k, inp.C)
-            w = eng.weights.packed(pack, self.weight, G.conv_fwd_pack(self.cout, inp.C, k))
-            cd = emit_conv(plan, ctx, inp, taps, w, self.bias, self.y, N=self.cout, OH=self.OH, OW=self.OW,
-                           in_stride=s, in_oh=inp.pad - p, in_ow=inp.pad - p)
-            if self.norm:
-                pre = attach_conv_stats(ctx, [cd], self.bias)
-            self._y_fallback(pre, [cd])
-        elif (self.kind == "rowpacked" and s == 1 and ctx.precision == 0 and OPT.split3 and OPT.pair_pixels and self.cout == 64
-              and (k + 1) * inp.C == 32 and self.OW % 2 == 0 and inp.wp % 2 == 0 and (inp.pad - p) % 2 == 0 and not self.y.is16):
+        if (self.kind == "rowpacked" and s == 1 and ctx.precision == 0 and OPT.split3 and OPT.pair_pixels and self.cout == 64
+                and (k + 1) * inp.C == 32 and self.OW % 2 == 0 and inp.wp % 2 == 0 and (inp.pad - p) % 2 == 0 and not self.y.is16):
             # Conv2d(3, 64, 7) on the split tile: TWO adjacent output pixels per GEMM row -- 128 columns, one tap per kernel row over the
             # 8 pixels x 4 channels both windows cover (a run of 32), the buffers viewed as pixel pairs (measured: DESIGN 3.1)
             cs = inp.C
@@ -1030,36 +1069,34 @@ class ConvIN:
             cd = emit_conv(plan, ctx, inp, G.Taps(list(range(k)), [0] * k, (k + 1) * cs), w, b2, self.y, N=2 * self.cout, OH=self.OH, OW=self.OW // 2,
                            in_oh=inp.pad - p, in_ow=(inp.pad - p) // 2, in_hw=(inp.hp, inp.wp // 2), in_cs=2 * cs,
                            out_hw=(self.y.hp, self.y.wp // 2), out_cs=2 * self.cout, out_span=2)
-            if self.norm:
-                pre = attach_conv_stats(ctx, [cd], self.bias)
-        elif self.kind == "rowpacked":
-            taps = G.conv_rowpacked_taps(k, inp.C)
-            w = eng.weights.packed(pack, self.weight, G.conv_rowpacked_pack(self.cout, self.cin, k, inp.C))
+        else:
+            taps, spec = self._direct_problem()
+            w = eng.weights.packed(pack, self.weight, spec)
             cd = emit_conv(plan, ctx, inp, taps, w, self.bias, self.y, N=self.cout, OH=self.OH, OW=self.OW,
                            in_stride=s, in_oh=inp.pad - p, in_ow=inp.pad - p)
-            if self.norm:
-                pre = attach_conv_stats(ctx, [cd], self.bias)
-            self._y_fallback(pre, [cd])
-        else:  # convT: 4 sub-pixel phases over the zero-halo-1 input, one launch
-            descs = None
-            phases = G.convT_fwd_phases(inp.H, inp.W, k, p)
-            if want_phase_pairs(ctx, phases, inp.C, self.cout, self.y):
-                descs = emit_phase_pairs(eng, pack, ctx, inp, phases, lambda hw: G.convT_fwd_pack(inp.C, self.cout, k, hw), self.weight,
-                                         self.bias, self.y, N=self.cout, in_off=inp.pad - 1, out_off=0)
-            for ph in (phases if descs is None else []):
-                descs = descs or []
-                taps = G.Taps(ph.dh, ph.dw, inp.C)
-                w = eng.weights.packed(pack, self.weight, G.convT_fwd_pack(inp.C, self.cout, k, ph.taps_hw))
-                descs.append(emit_conv(None, ctx, inp, taps, w, self.bias, self.y, N=self.cout, OH=ph.n_h, OW=ph.n_w,
-                                       in_oh=ph.in_oh + inp.pad - 1, in_ow=ph.in_ow + inp.pad - 1,
-                                       out_stride=2, out_oh=ph.out_oh, out_ow=ph.out_ow))
-            if self.norm:
-                pre = attach_conv_stats(ctx, descs, self.bias)
-            self._y_fallback(pre, descs)
-            emit_conv_group(plan, ctx, descs)
-        emit_in_fwd(plan, ctx, self.y, self.out, norm=self.norm, act=(L.ACT_NONE if self.keep_z else self.act),
-                    residual=self.residual, border=self.out_border, stats=self.stats, ws=(pre[2] if pre is not None else eng.scratch.get()),
-                    stats_only=getattr(self, "defer_apply", False), pre_stats=(pre[:2] if pre is not None else None))
+        return self._conv_stats([cd])
+
+    def _phase_descs(self, pack: Plan, src: Halo, dst: Halo, phases: list, spec_fn, bias, *, run, N, in_off, out_off, may_pair=True):
+        """The convolution descriptors (not yet launched) of a stride-2 gather's sub-pixel phases from `src` into `dst`: the two paired
+        problems where want_phase_pairs says so and the phases pair up, else one problem per phase.  spec_fn(taps_hw) -> PackSpec."""
+        eng, ctx = self.eng, self.eng.ctx
+        descs = None
+        if may_pair and want_phase_pairs(ctx, phases, run, N, dst):
+            descs = emit_phase_pairs(eng, pack, ctx, src, phases, spec_fn, self.weight, bias, dst, N=N, in_off=in_off, out_off=out_off)
+        if descs is None:
+            descs = []
+            for ph in phases:
+                w = eng.weights.packed(pack, self.weight, spec_fn(ph.taps_hw))
+                descs.append(emit_conv(None, ctx, src, G.Taps(ph.dh, ph.dw, run), w, bias, dst, N=N, OH=ph.n_h, OW=ph.n_w,
+                                       in_oh=ph.in_oh + in_off, in_ow=ph.in_ow + in_off,
+                                       out_stride=2, out_oh=ph.out_oh + out_off, out_ow=ph.out_ow + out_off))
+        return descs
+
+    def _conv_stats(self, descs):
+        """Let the direct-tile launches of the forward leave the instance norm's partial sums where they qualify (attach_conv_stats)."""
+        pre = attach_conv_stats(self.eng.ctx, descs, self.bias) if self.norm else None
+        self._y_fallback(pre, descs)
+        return pre
 
     def _y_fallback(self, pre, descs):
         """y was allocated as bf16 on the prediction that the launch leaves the statistics; it did not (split-K): back to fp32."""
@@ -1078,7 +1115,7 @@ class ConvIN:
         else:
             zpad = 1 if need_dgrad else 0
         self.dy = Halo(ctx, self.inp.B, self.OH, self.OW, self.cout, zpad, twin=True)
-        self.eng.__dict__.setdefault("twinned", []).append(self.dy)
+        self.eng.twinned.append(self.dy)
 
     def emit_bwd(self, plan: Plan, pack: Plan, *, g: Optional[Halo], g_fold=False, g2: Optional[Halo] = None,
                  gsum: Optional[Halo] = None, gw: Optional[torch.Tensor], gb: Optional[torch.Tensor], dgrad_out: Optional[Halo],
@@ -1087,143 +1124,140 @@ class ConvIN:
         k, s, p = self.k, self.s, self.p
         act = self.act if act is None else act
         dy = self.dy
-        # Winograd backward (below).  (Round 2 measured the second pass of the instance-norm backward evaluated INSIDE the per-thread dY
-        # transform at 161 us against 84 + 31 per layer -- every dY element re-derived by the 2.25 patches that contain it, at 240 VGPRs.
-        # The lane-spread transform of round 3 has the registers for it: OPT.fuse_dy_norm.)
+        # Winograd backward (_emit_w6_backward).  (Round 2 measured the second pass of the instance-norm backward evaluated INSIDE the
+        # per-thread dY transform at 161 us against 84 + 31 per layer -- every dY element re-derived by the 2.25 patches that contain it,
+        # at 240 VGPRs.  The lane-spread transform of round 3 has the registers for it: OPT.fuse_dy_norm.)
         w6_bwd = (self.kind == "conv" and s == 1 and gw is not None and dgrad_out is not None and dgrad_out.pad == p and dy.pad == k - 1
                   and wino_dgrad_applicable(ctx, k, s, dgrad_out, self.cout, inp.C) and inp.C > 64
                   and inp.pad == 1 and p == 1 and self.cout % 128 == 0)
         fuse_dy = (w6_bwd and k == 3 and self.norm and dy.t16 is None and OPT.fuse_dy_norm and wino6_variant(3) == 6
                    and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU))
-        # The gradient arrives from an F(6x6,3x3) data gradient over the padded extent (reflect halo of 1 to fold): that launch's output
-        # transform is switched to its fused mode -- it folds the halo in registers (lane pairs exchange half tiles so that the per-pixel
-        # phase moves 16 bytes per lane), adds the skip gradient, stores the folded gradient dense and leaves the partial sums of this
-        # layer's first backward pass; the halo'd buffer `g` is then never written or read.  The first pass disappears (94 -> 45 us per
-        # layer) for an output transform of 67 us instead of 39: 21.16 -> 20.87 ms per step.  OPT.fuse_inbwd = False keeps the two passes.
-        pre_sums, ws = 0, eng.scratch.get()
-        od = getattr(g, "w6_out_desc", None) if g is not None else None
-        if od is not None and od.r == 6 and g_fold and self.norm and g.pad == 1 and dy.t16 is None and OPT.fuse_inbwd:
-            mo = _w6_geo(od.r if od.r else 3)[0]
-            Hp, Wp = od.H, od.W
-            if (Hp == self.OH + 2 and Wp == self.OW + 2 and od.K == self.cout and od.B == inp.B and min(Hp, Wp) >= 6
-                    and (Hp - 3) // mo == (Hp - 1) // mo and (Wp - 3) // mo == (Wp - 1) // mo):
-                chunks = (-(-Hp // mo)) * (-(-Wp // mo))
-                if gsum is None:                   # no skip path: the folded gradient lives in a pooled dense buffer until the second pass
-                    key = ("inbwd_gz", inp.B, self.OH, self.OW, self.cout)
-                    pool = ctx.__dict__.setdefault("inbwd_pool", {})
-                    if key not in pool:
-                        pool[key] = Halo(ctx, inp.B, self.OH, self.OW, self.cout, 0)
-                    gsum = pool[key]
-                if not hasattr(ctx, "inbwd_part"):
-                    ctx.inbwd_part = SplitPool(ctx)
-                ws = ctx.inbwd_part.get(inp.B * chunks * 2 * self.cout + inp.B * 2 * self.cout)
-                od.fuse_y, od.fuse_mean, od.fuse_rstd = self.y.ptr, self.stats[0].data_ptr(), self.stats[1].data_ptr()
-                od.fuse_g2 = g2.ptr if g2 is not None else None
-                od.fuse_gz, od.fuse_part, od.fuse_part_elems = gsum.ptr, ws.data_ptr(), ws.numel()
-                od.fuse_act, od.fuse_slope = act, 0.2
-                pre_sums = chunks
-        # The gradient arrives from direct-tile data-gradient launches (the sub-pixel phases of a stride-2 convolution, or a transposed
-        # convolution's strided one): their epilogue takes this layer's first backward pass next to the store (nirgan_conv_desc.fuse_*).
-        # Worth it on the large maps only (threshold as for the forward statistics); OPT.fuse_inbwd = False keeps the separate pass.
-        cds = getattr(g, "conv_out_descs", None) if g is not None else None
-        if (cds and not pre_sums and self.norm and not g_fold and g2 is None and gsum is None and self.cout % 4 == 0
+        # the instance norm's backward: its first pass inside the launch that produced g where that launch can take it
+        scratch = eng.scratch.get()
+        pre_sums, ws, gsum = (self._first_pass_from_w6_output(g, g_fold, g2, gsum, act)
+                              or self._first_pass_from_conv_epilogues(g, g_fold, g2, gsum, act) or (0, scratch, gsum))
+        nd = emit_in_bwd(plan, ctx, g=g, g_fold=g_fold, g2=g2, act=act, y=self.y, stats=self.stats, norm=self.norm, dy=self.dy, gsum=gsum,
+                         dbias=(None if self.norm else gb),   # a bias in front of InstanceNorm has gradient exactly 0: left at 0
+                         ws=ws, shape=(inp.B, self.OH, self.OW, self.cout), pre_sums=pre_sums, sums_only=fuse_dy)
+        if w6_bwd:                # stride-1 convolutions that need both gradients: Winograd ...
+            self._emit_w6_backward(plan, pack, gw, dgrad_out, nd if fuse_dy else None)
+        elif self.kind == "conv" and s == 1 and gw is not None and dgrad_out is not None:       # ... or the direct tiles
+            self._emit_paired_s1(plan, pack, gw, dgrad_out)
+        else:
+            if gw is not None:         # (None: the parameters are frozen)
+                self._emit_wgrad(plan, gw)
+            if dgrad_out is not None:
+                self._emit_dgrad(plan, pack, dgrad_out, frozen=gw is None)
+
+    def _first_pass_from_w6_output(self, g, g_fold, g2, gsum, act):
+        """The gradient arrives from an F(6x6,3x3) data gradient over the padded extent (reflect halo of 1 to fold): that launch's output
+        transform is switched to its fused mode -- it folds the halo in registers (lane pairs exchange half tiles so that the per-pixel
+        phase moves 16 bytes per lane), adds the skip gradient, stores the folded gradient dense and leaves the partial sums of this
+        layer's first backward pass; the halo'd buffer `g` is then never written or read.  The first pass disappears (94 -> 45 us per
+        layer) for an output transform of 67 us instead of 39: 21.16 -> 20.87 ms per step.  OPT.fuse_inbwd = False keeps the two passes.
+        Returns (chunks per sample, workspace of the partial sums, dense folded gradient) with g.w6_out_desc armed, or None."""
+        ctx, inp = self.eng.ctx, self.inp
+        od = g.w6_out_desc if g is not None else None
+        if not (od is not None and od.r == 6 and g_fold and self.norm and g.pad == 1 and self.dy.t16 is None and OPT.fuse_inbwd):
+            return None
+        mo, Hp, Wp = _w6_geo(od.r if od.r else 3)[0], od.H, od.W
+        if not (Hp == self.OH + 2 and Wp == self.OW + 2 and od.K == self.cout and od.B == inp.B and min(Hp, Wp) >= 6
+                and (Hp - 3) // mo == (Hp - 1) // mo and (Wp - 3) // mo == (Wp - 1) // mo):
+            return None
+        chunks = (-(-Hp // mo)) * (-(-Wp // mo))
+        if gsum is None:                   # no skip path: the folded gradient lives in a pooled dense buffer until the second pass
+            gsum = ctx.pool(("inbwd_gz", inp.B, self.OH, self.OW, self.cout), lambda: Halo(ctx, inp.B, self.OH, self.OW, self.cout, 0))
+        ws = ctx.pool("inbwd_part").get(inp.B * chunks * 2 * self.cout + inp.B * 2 * self.cout)
+        od.fuse_y, od.fuse_mean, od.fuse_rstd = self.y.ptr, self.stats[0].data_ptr(), self.stats[1].data_ptr()
+        od.fuse_g2 = g2.ptr if g2 is not None else None
+        od.fuse_gz, od.fuse_part, od.fuse_part_elems = gsum.ptr, ws.data_ptr(), ws.numel()
+        od.fuse_act, od.fuse_slope = act, 0.2
+        return chunks, ws, gsum
+
+    def _first_pass_from_conv_epilogues(self, g, g_fold, g2, gsum, act):
+        """The gradient arrives from direct-tile data-gradient launches (the sub-pixel phases of a stride-2 convolution, or a transposed
+        convolution's strided one): their epilogue takes this layer's first backward pass next to the store (nirgan_conv_desc.fuse_*).
+        Worth it on the large maps only (threshold as for the forward statistics); OPT.fuse_inbwd = False keeps the separate pass.
+        Returns (chunks per sample, workspace of the partial sums, None) with g.conv_out_descs armed, or None."""
+        ctx, inp = self.eng.ctx, self.inp
+        cds = g.conv_out_descs if g is not None else None
+        if not (cds and self.norm and not g_fold and g2 is None and gsum is None and self.cout % 4 == 0
                 and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU) and OPT.fuse_inbwd
                 and all(c.ksplit <= 1 and (c.OH * c.OW) % 128 == 0 and channels_of(c) == self.cout and not c.bias for c in cds)
                 and sum(c.OH * c.OW * max(1, c.out_span) for c in cds) == self.OH * self.OW
                 and self.OH * self.OW >= (OPT.epilogue_min_pixels if ctx.precision == 0 else min(OPT.epilogue_min_pixels, OPT.epilogue_min_pixels_bf16))):
-            chunks = sum(c.OH * c.OW // 128 * max(1, c.out_span) for c in cds)
-            if not hasattr(ctx, "inbwd_part"):
-                ctx.inbwd_part = SplitPool(ctx)
-            ws = ctx.inbwd_part.get(inp.B * chunks * 2 * self.cout + inp.B * 2 * self.cout)
-            first = 0
-            for c in cds:
-                c.fuse_y, c.fuse_mean, c.fuse_rstd = self.y.ptr_any(), self.stats[0].data_ptr(), self.stats[1].data_ptr()
-                c.fuse_y_bf16 = 1 if self.y.is16 else 0
-                c.fuse_h, c.fuse_w = self.OH, self.OW
-                c.fuse_oh, c.fuse_ow = c.out_oh - g.pad, c.out_ow - g.pad
-                c.fuse_act, c.fuse_slope = act, 0.2
-                c.fuse_part, c.fuse_part_elems, c.fuse_chunk0, c.fuse_chunks = ws.data_ptr(), ws.numel(), first, chunks
-                first += c.OH * c.OW // 128 * max(1, c.out_span)
-            pre_sums = chunks
-        nd = emit_in_bwd(plan, ctx, g=g, g_fold=g_fold, g2=g2, act=act,
-                         y=self.y, stats=self.stats, norm=self.norm, dy=self.dy, gsum=gsum,
-                         dbias=(None if self.norm else gb),   # a bias in front of InstanceNorm has gradient exactly 0: left at 0
-                         ws=ws,
-                         shape=(inp.B, self.OH, self.OW, self.cout), pre_sums=pre_sums, sums_only=fuse_dy)
-        # stride-1 convolutions that need both gradients
-        if w6_bwd:
-            # Winograd: data gradient and transform-domain weight gradient, dY read once for both of its transforms
-            wd6 = emit_wino6(None, pack, ctx, dy, self.weight, None, _FullExtent(dgrad_out), H=dgrad_out.hp, W=dgrad_out.wp,
-                             cin=self.cout, cout=inp.C, flip=True, r=k)
-            keepV = getattr(self, "wino_fwd_keeps_V", False) and getattr(self, "wino6", False)
-            emit_wino6_backward(plan, ctx, dy, inp, gw, OH=self.OH, OW=self.OW, cin=inp.C, cout=self.cout, slabs_pool=eng.slabs,
-                                dgrad=wd6, V_fwd=(self.wino_fwd if keepV else None), r=k, norm_desc=(nd if fuse_dy else None))
-            if k == 3:
-                dgrad_out.w6_out_desc = wd6          # the consumer of this gradient may switch the output transform to its fused mode
-            return
-        # direct tiles: one fused launch (data-gradient tiles + weight-gradient tiles)
-        if self.kind == "conv" and s == 1 and gw is not None and dgrad_out is not None:
-            assert dgrad_out.H == inp.H and dgrad_out.pad == p and dy.pad == k - 1
-            hw = [(kh, kw) for kh in range(k) for kw in range(k)]
-            wd = eng.weights.packed(pack, self.weight, G.conv_dgrad_pack(self.cout, inp.C, k, hw))
-            cdesc = emit_conv(None, ctx, dy, G.conv_dgrad_s1_taps(k, self.cout), wd, None, dgrad_out, N=inp.C,
-                              OH=dgrad_out.hp, OW=dgrad_out.wp)
-            emit_wgrad(plan, ctx, dy, inp, G.conv_fwd_taps(k, inp.C), G.conv_fwd_pack(self.cout, inp.C, k), gw,
-                       N=self.cout, OH=self.OH, OW=self.OW, p_oh=dy.pad, p_ow=dy.pad, q_stride=s,
-                       q_oh=inp.pad - p, q_ow=inp.pad - p, slabs_pool=eng.slabs, pair_with=cdesc)
-            return
-        # weight gradient (skipped when the parameters are frozen: gw is None)
-        if gw is None:
-            pass
-        elif self.kind == "conv":
-            emit_wgrad(plan, ctx, dy, inp, G.conv_fwd_taps(k, inp.C), G.conv_fwd_pack(self.cout, inp.C, k), gw,
-                       N=self.cout, OH=self.OH, OW=self.OW, p_oh=dy.pad, p_ow=dy.pad, q_stride=s,
-                       q_oh=inp.pad - p, q_ow=inp.pad - p, slabs_pool=eng.slabs)
-        elif self.kind == "rowpacked" and s == 1 and emit_wgrad_pixel_pairs(plan, ctx, dy, inp, gw, k=k, p=p, cin=self.cin, cout=self.cout,
-                                                                            OH=self.OH, OW=self.OW):
-            pass
-        elif self.kind == "rowpacked":
-            emit_wgrad(plan, ctx, dy, inp, G.conv_rowpacked_taps(k, inp.C), G.conv_rowpacked_pack(self.cout, self.cin, k, inp.C), gw,
-                       N=self.cout, OH=self.OH, OW=self.OW, p_oh=dy.pad, p_ow=dy.pad, q_stride=s,
-                       q_oh=inp.pad - p, q_ow=inp.pad - p, slabs_pool=eng.slabs)
-        else:  # convT: rows = input channels, gathered side = dY with stride 2
+            return None
+        chunks = sum(c.OH * c.OW // 128 * max(1, c.out_span) for c in cds)
+        ws = ctx.pool("inbwd_part").get(inp.B * chunks * 2 * self.cout + inp.B * 2 * self.cout)
+        first = 0
+        for c in cds:
+            c.fuse_y, c.fuse_mean, c.fuse_rstd = self.y.ptr_any(), self.stats[0].data_ptr(), self.stats[1].data_ptr()
+            c.fuse_y_bf16 = 1 if self.y.is16 else 0
+            c.fuse_h, c.fuse_w = self.OH, self.OW
+            c.fuse_oh, c.fuse_ow = c.out_oh - g.pad, c.out_ow - g.pad
+            c.fuse_act, c.fuse_slope = act, 0.2
+            c.fuse_part, c.fuse_part_elems, c.fuse_chunk0, c.fuse_chunks = ws.data_ptr(), ws.numel(), first, chunks
+            first += c.OH * c.OW // 128 * max(1, c.out_span)
+        return chunks, ws, None
+
+    def _emit_w6_backward(self, plan: Plan, pack: Plan, gw, dgrad_out: Halo, norm_desc):
+        """Winograd: data gradient and transform-domain weight gradient, dY read once for both of its transforms."""
+        eng, ctx, inp, dy, k = self.eng, self.eng.ctx, self.inp, self.dy, self.k
+        wd6 = emit_wino6(None, pack, ctx, dy, self.weight, None, _FullExtent(dgrad_out), H=dgrad_out.hp, W=dgrad_out.wp,
+                         cin=self.cout, cout=inp.C, flip=True, r=k)
+        V_fwd = self.wino_fwd if self.wino_fwd_keeps_V and self.wino6 else None
+        emit_wino6_backward(plan, ctx, dy, inp, gw, OH=self.OH, OW=self.OW, cin=inp.C, cout=self.cout, slabs_pool=eng.slabs,
+                            dgrad=wd6, V_fwd=V_fwd, r=k, norm_desc=norm_desc)
+        if k == 3:
+            dgrad_out.w6_out_desc = wd6          # the consumer of this gradient may switch the output transform to its fused mode
+
+    def _dgrad_s1_desc(self, plan: Optional[Plan], pack: Plan, dgrad_out: Halo):
+        """Stride-1 data gradient on the direct tiles, a full correlation: gradient wrt the halo'd input (size H+2p), folded / cropped by
+        the consumer.  plan = None: the descriptor only (the caller launches it with the weight gradient)."""
+        k, inp = self.k, self.inp
+        assert dgrad_out.H == inp.H and dgrad_out.pad == self.p and self.dy.pad == k - 1
+        hw = [(kh, kw) for kh in range(k) for kw in range(k)]
+        w = self.eng.weights.packed(pack, self.weight, G.conv_dgrad_pack(self.cout, inp.C, k, hw))
+        return emit_conv(plan, self.eng.ctx, self.dy, G.conv_dgrad_s1_taps(k, self.cout), w, None, dgrad_out, N=inp.C,
+                         OH=dgrad_out.hp, OW=dgrad_out.wp)
+
+    def _emit_direct_wgrad(self, plan: Plan, gw, pair_with=None):
+        inp, dy, p = self.inp, self.dy, self.p
+        taps, spec = self._direct_problem()
+        emit_wgrad(plan, self.eng.ctx, dy, inp, taps, spec, gw, N=self.cout, OH=self.OH, OW=self.OW, p_oh=dy.pad, p_ow=dy.pad,
+                   q_stride=self.s, q_oh=inp.pad - p, q_ow=inp.pad - p, slabs_pool=self.eng.slabs, pair_with=pair_with)
+
+    def _emit_paired_s1(self, plan: Plan, pack: Plan, gw, dgrad_out: Halo):
+        """direct tiles: one fused launch (data-gradient tiles + weight-gradient tiles)"""
+        self._emit_direct_wgrad(plan, gw, pair_with=self._dgrad_s1_desc(None, pack, dgrad_out))
+
+    def _emit_wgrad(self, plan: Plan, gw):
+        ctx, inp, dy, k, p = self.eng.ctx, self.inp, self.dy, self.k, self.p
+        if self.kind not in ("conv", "rowpacked"):  # convT: rows = input channels, gathered side = dY with stride 2
             emit_wgrad(plan, ctx, inp, dy, G.convT_dgrad_taps(k, self.cout), G.convT_dgrad_pack(inp.C, self.cout, k), gw,
                        N=inp.C, OH=inp.H, OW=inp.W, p_oh=inp.pad, p_ow=inp.pad, q_stride=2,
-                       q_oh=dy.pad - p, q_ow=dy.pad - p, slabs_pool=eng.slabs)
-        # data gradient
-        if dgrad_out is None:
-            return
+                       q_oh=dy.pad - p, q_ow=dy.pad - p, slabs_pool=self.eng.slabs)
+        elif not (self.kind == "rowpacked" and self.s == 1
+                  and emit_wgrad_pixel_pairs(plan, ctx, dy, inp, gw, k=k, p=p, cin=self.cin, cout=self.cout, OH=self.OH, OW=self.OW)):
+            self._emit_direct_wgrad(plan, gw)
+
+    def _emit_dgrad(self, plan: Plan, pack: Plan, dgrad_out: Halo, frozen: bool):
+        eng, ctx, inp, dy = self.eng, self.eng.ctx, self.inp, self.dy
+        k, s, p = self.k, self.s, self.p
         if self.kind == "conv" and s == 1:
-            # full correlation: gradient wrt the halo'd input (size H+2p), folded / cropped by the consumer
             assert dgrad_out.H == inp.H and dgrad_out.pad == p and dy.pad == k - 1
-            if gw is None and wino_dgrad_applicable(ctx, k, s, dgrad_out, self.cout, inp.C) and inp.C > 64:
+            if frozen and wino_dgrad_applicable(ctx, k, s, dgrad_out, self.cout, inp.C) and inp.C > 64:
                 # frozen parameters (the discriminator inside the generator step): the data gradient alone, as a Winograd convolution
                 emit_wino6(plan, pack, ctx, dy, self.weight, None, _FullExtent(dgrad_out), H=dgrad_out.hp, W=dgrad_out.wp,
                            cin=self.cout, cout=inp.C, flip=True, r=k)
-                return
-            taps = G.conv_dgrad_s1_taps(k, self.cout)
-            hw = [(kh, kw) for kh in range(k) for kw in range(k)]
-            w = eng.weights.packed(pack, self.weight, G.conv_dgrad_pack(self.cout, inp.C, k, hw))
-            emit_conv(plan, ctx, dy, taps, w, None, dgrad_out, N=inp.C, OH=dgrad_out.hp, OW=dgrad_out.wp)
+            else:
+                self._dgrad_s1_desc(plan, pack, dgrad_out)
         elif self.kind in ("conv", "rowpacked") and s == 2:
             assert dgrad_out.H == inp.H and dy.pad == 1
-            cin_buf = inp.C
-            descs = None
-            phases = G.conv_dgrad_s2_phases(inp.H, inp.W, k, p)
-            if self.kind == "conv" and want_phase_pairs(ctx, phases, self.cout, inp.C, dgrad_out):
-                descs = emit_phase_pairs(eng, pack, ctx, dy, phases, lambda hw: G.conv_dgrad_pack(self.cout, inp.C, k, hw), self.weight, None,
-                                         dgrad_out, N=inp.C, in_off=0, out_off=dgrad_out.pad)
-            for ph in (phases if descs is None else []):
-                descs = descs or []
-                if self.kind == "conv":
-                    spec = G.conv_dgrad_pack(self.cout, inp.C, k, ph.taps_hw)
-                else:
-                    spec = G.conv_dgrad_pack(self.cout, self.cin, k, ph.taps_hw)
-                    cin_buf = self.cin
-                w = eng.weights.packed(pack, self.weight, spec)
-                descs.append(emit_conv(None, ctx, dy, G.Taps(ph.dh, ph.dw, self.cout), w, None, dgrad_out, N=cin_buf,
-                                       OH=ph.n_h, OW=ph.n_w, in_oh=ph.in_oh, in_ow=ph.in_ow, out_stride=2,
-                                       out_oh=ph.out_oh + dgrad_out.pad, out_ow=ph.out_ow + dgrad_out.pad))
+            cin = inp.C if self.kind == "conv" else self.cin
+            descs = self._phase_descs(pack, dy, dgrad_out, G.conv_dgrad_s2_phases(inp.H, inp.W, k, p),
+                                      lambda hw: G.conv_dgrad_pack(self.cout, cin, k, hw), None, run=self.cout, N=cin,
+                                      in_off=0, out_off=dgrad_out.pad, may_pair=self.kind == "conv")
             emit_conv_group(plan, ctx, descs)
             dgrad_out.conv_out_descs = descs             # the consumer of this gradient may have the epilogues take its first backward pass
         elif self.kind == "convT":

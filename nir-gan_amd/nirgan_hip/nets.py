@@ -16,7 +16,7 @@ import torch
 from . import geometry as G
 from . import lib as L
 from .options import OPT
-from .engine import (ConvIN, Ctx, Halo, Plan, SlabPool, TapPlaneConv, Weights, _Scratch, drop_dead_fp32_stores, emit_conv, grad_halo,
+from .engine import (ConvIN, Ctx, Halo, LayerHost, Plan, TapPlaneConv, drop_dead_fp32_stores, emit_conv, grad_halo,
                      emit_deferred_reduce_rows, emit_w6_deferred_finishes, emit_wgrad, wino_applicable)
 
 
@@ -26,12 +26,9 @@ def generator_layout(n_blocks: int) -> dict:
     return {"first": 1, "down": [4, 7], "blocks": list(range(10, 10 + n_blocks)), "up": [up0, up0 + 3], "last": up0 + 7}
 
 
-class _Engine:
-    def __init__(self, device, precision="fp32"):
-        self.ctx = Ctx(device, precision)
-        self.weights = Weights(self.ctx)
-        self.slabs = SlabPool(self.ctx)
-        self.scratch = _Scratch(self.ctx)
+class _Engine(LayerHost):
+    def __init__(self, device, precision="fp32", keep_wino_V: bool = False):
+        super().__init__(Ctx(device, precision), keep_wino_V)
         self.pack_fwd, self.pack_bwd = Plan(self.ctx), Plan(self.ctx)
         self.fwd, self.bwd = Plan(self.ctx), Plan(self.ctx)
         self._packed_version = -1
@@ -39,7 +36,7 @@ class _Engine:
 
     def refresh_weights(self, version: int, backward: bool = False):
         """Re-pack weights when the parameters changed (version = optimizer step counter)."""
-        if not getattr(self, "_packs_fused", False):
+        if not self._packs_fused:
             for pl in (self.pack_fwd, self.pack_bwd):
                 pl.fuse_packs()
                 pl.fuse_wino6_weights()
@@ -59,8 +56,7 @@ class GeneratorEngine(_Engine):
                  B: int, H: int, W: int, data_pad: int = 0, inject: Optional[dict] = None, need_backward: bool = True,
                  precision="fp32"):
         dev = params["model.1.weight"].device
-        super().__init__(dev, precision)
-        self.need_backward = need_backward
+        super().__init__(dev, precision, keep_wino_V=need_backward)
         ctx = self.ctx
         self.params, self.grads = params, grads
         self.n_blocks, self.B, self.H, self.W, self.data_pad = n_blocks, B, H, W, data_pad
@@ -82,12 +78,11 @@ class GeneratorEngine(_Engine):
         self.x4 = Halo(ctx, B, Hg, Wg, 4, 3)
         self.L1 = ConvIN(self, "first", "rowpacked", self.x4, P(1, "weight"), P(1, "bias"), k=7, s=1, p=3, cout=ngf,
                          out_pad=1, cin_real=in_nc)
-        if inject is None:
-            self.L2 = ConvIN(self, "down0", "conv", self.L1.out, P(4, "weight"), P(4, "bias"), k=3, s=2, p=1, cout=2 * ngf, out_pad=1)
-            l2_out = self.L2.out
-        else:
-            self.L2 = ConvIN(self, "down0", "conv", self.L1.out, P(4, "weight"), P(4, "bias"), k=3, s=2, p=1, cout=2 * ngf,
-                             out_pad=0, keep_z=True)
+        # (inject: L2.out holds z dense, the modulation writes the activated, halo'd tensor a2)
+        self.L2 = ConvIN(self, "down0", "conv", self.L1.out, P(4, "weight"), P(4, "bias"), k=3, s=2, p=1, cout=2 * ngf,
+                         out_pad=(1 if inject is None else 0), keep_z=inject is not None)
+        l2_out = self.L2.out
+        if inject is not None:
             H2, W2 = self.L2.OH, self.L2.OW
             if H2 != W2:
                 raise ValueError("SatCLIP injection needs square tiles (generator_inject.py:116 swaps H and W)")
@@ -110,8 +105,7 @@ class GeneratorEngine(_Engine):
             # c1's normalised output has ONE reader, c2's Winograd input transform: fold InstanceNorm + ReLU + reflect pad into that
             # transform and never write the buffer.  Needs c2's V kept for its weight gradient (else the backward re-reads c1.out).
             if wino_applicable(self.ctx, c2.inp, 3, 1, 1, c2.cout, c2.OH, c2.OW) and OPT.fold_apply:
-                c1.defer_apply = True
-                c2.producer = c1
+                c2.fold_producer_apply(c1)
             self.blocks.append((i, c1, c2))
             u = c2.out
         i0, i1 = lay["up"]
@@ -147,7 +141,7 @@ class GeneratorEngine(_Engine):
         if need_backward:
             self._build_backward()
         # bf16 operand mode: activations / output gradients that every reader takes from the bf16 twin are stored as bf16 only
-        drop_dead_fp32_stores(getattr(self, "twinned", []))
+        drop_dead_fp32_stores(self.twinned)
 
     # ------------------------------------------------------------------ SatCLIP injection
     def _emit_inject_fwd(self, f: Plan):
@@ -216,8 +210,7 @@ class GeneratorEngine(_Engine):
             b.add("nirgan_fill", gpc.data_ptr(), 1, 0.0)
             b.add("nirgan_param_scale_bwd", self.dpred.data_ptr(), self.pred_raw.data_ptr(), self.params["post_correction_param"].data_ptr(),
                   self.last.dout.data_ptr(), gpc.data_ptr(), self.pc_ws.data_ptr(), self.pc_ws.numel(), self.dpred.numel())
-        for layer in [self.L1]:
-            layer.alloc_bwd(need_dgrad=False)
+        self.L1.alloc_bwd(need_dgrad=False)
         for layer in [self.L2, self.L3, self.U1, self.U2] + [c for _, c1, c2 in self.blocks for c in (c1, c2)]:
             layer.alloc_bwd(need_dgrad=True)
         # the only live generator bias (last conv) is accumulated with atomics: zero it first.  Biases in front
@@ -287,23 +280,80 @@ class GeneratorEngine(_Engine):
         self.bwd.run()
 
 
-class DiscriminatorEngine(_Engine):
+class _DiscriminatorFrontEnd(_Engine):
+    """The input side and the run methods both discriminators share: the NCHW staging tensor `x_in`, the [B][H+2p][W+2p][4] input `x4`
+    (halo pad p: 1 for the PatchGAN's first convolution, 0 for the per-pixel network), the plans that fill it, and the dispatch of
+    forward / backward over the plans fwd, bwd, bwd_frozen, bwd_pred a subclass builds (with out, dout, gx4, gpred)."""
+
+    def __init__(self, params, grads, B: int, H: int, W: int, device, precision):
+        # No discriminator layer keeps the V of a Winograd forward resident (its stride-1 4x4 layer re-transforms the input in the
+        # backward).  This states what the engines have always done; keeping V changes the plans and the resident memory and is a
+        # separate, measured change.
+        super().__init__(device, precision, keep_wino_V=False)
+        self.params, self.grads, self.B, self.H, self.W = params, grads, B, H, W
+        self._part_plans: dict = {}
+
+    def _alloc_input(self, pad: int):
+        ctx, B, H, W = self.ctx, self.B, self.H, self.W
+        self.x_in = ctx.zeros(B, 4, H, W)
+        self.x4 = Halo(ctx, B, H, W, 4, pad)
+        self.in_plan = Plan(ctx)
+        self.in_plan.add("nirgan_nchw_to_halo", self.x_in.data_ptr(), B, 4, H, W, self.x4.ptr, 4, 0, 0, pad, L.BORDER_KEEP)
+
+    def input_plan(self, parts) -> Plan:
+        """parts: list of (NCHW tensor [nb, Cs, H, W], b0, c0) written straight into the halo'd input
+        (the torch.cat of model/pix2pix.py:197,202,216 never materialises)."""
+        key = tuple((t.data_ptr(), t.shape[0], t.shape[1], b0, c0) for t, b0, c0 in parts)
+        if key not in self._part_plans:
+            pl = Plan(self.ctx)
+            for t, b0, c0 in parts:
+                nb, cs = t.shape[0], t.shape[1]
+                assert t.is_contiguous() and t.shape[2] == self.H and t.shape[3] == self.W and b0 + nb <= self.B
+                dst = self.x4.ptr + b0 * self.x4.hp * self.x4.wp * 4 * 4
+                pl.add("nirgan_nchw_to_halo", t.data_ptr(), nb, cs, self.H, self.W, dst, 4, c0, 0, self.x4.pad, L.BORDER_KEEP)
+            self._part_plans[key] = pl
+        return self._part_plans[key]
+
+    def forward(self, x: Optional[torch.Tensor] = None, parts=None, version: int = 0) -> torch.Tensor:
+        self.refresh_weights(version)
+        if parts is not None:
+            self.input_plan(parts).run()
+        else:
+            self.x_in.copy_(x)
+            self.in_plan.run()
+        self.fwd.run()
+        return self.out
+
+    def backward(self, dout: Optional[torch.Tensor], frozen: bool = False, version: int = 0, pred_only: bool = False) -> Optional[torch.Tensor]:
+        """frozen=False: parameter gradients.  frozen=True: gradient wrt the input ([B][H][W][4]), or wrt its
+        channel 3 only ([B][H][W]) when pred_only."""
+        self.refresh_weights(version, backward=True)
+        if dout is not None:
+            self.dout.copy_(dout)
+        if not frozen:
+            self.bwd.run()
+            return None
+        if pred_only:
+            self.bwd_pred.run()
+            return self.gpred
+        self.bwd_frozen.run()
+        return self.gx4.t
+
+
+class DiscriminatorEngine(_DiscriminatorFrontEnd):
     """NLayerDiscriminator(input_nc=4, ndf, n_layers=3, InstanceNorm): 70x70 PatchGAN."""
 
     def __init__(self, params: Dict[str, torch.Tensor], grads: Optional[Dict[str, torch.Tensor]], B: int, H: int, W: int,
                  need_backward: bool = True, precision="fp32"):
-        dev = params["model.0.weight"].device
-        super().__init__(dev, precision)
+        super().__init__(params, grads, B, H, W, params["model.0.weight"].device, precision)
         ctx = self.ctx
-        self.params, self.grads, self.B, self.H, self.W = params, grads, B, H, W
         ndf, in_nc = params["model.0.weight"].shape[0], params["model.0.weight"].shape[1]
         assert in_nc == 4, "PatchGAN input is cat(rgb, nir) = 4 channels on this path"
 
         def P(i, what):
             return params[f"model.{i}.{what}"]
 
-        self.x_in = ctx.zeros(B, 4, H, W)
-        self.x4 = Halo(ctx, B, H, W, 4, 1)
+        self._alloc_input(pad=1)
         self.C1 = ConvIN(self, "c1", "rowpacked", self.x4, P(0, "weight"), P(0, "bias"), k=4, s=2, p=1, cout=ndf, norm=False,
                          act=L.ACT_LRELU, out_pad=1, cin_real=4)
         self.C2 = ConvIN(self, "c2", "conv", self.C1.out, P(2, "weight"), P(2, "bias"), k=4, s=2, p=1, cout=2 * ndf, act=L.ACT_LRELU, out_pad=1)
@@ -311,15 +361,11 @@ class DiscriminatorEngine(_Engine):
         self.C4 = ConvIN(self, "c4", "conv", self.C3.out, P(8, "weight"), P(8, "bias"), k=4, s=1, p=1, cout=8 * ndf, act=L.ACT_LRELU, out_pad=1)
         self.C5 = TapPlaneConv(self, "c5", self.C4.out, P(11, "weight"), P(11, "bias"), k=4, p=1)
         self.out = self.C5.dst
-        f, pk = self.fwd, self.pack_fwd
-        self.in_plan = Plan(ctx)
-        self.in_plan.add("nirgan_nchw_to_halo", self.x_in.data_ptr(), B, 4, H, W, self.x4.ptr, 4, 0, 0, 1, L.BORDER_KEEP)
         for layer in (self.C1, self.C2, self.C3, self.C4, self.C5):
-            layer.emit_fwd(f, pk)
-        self._part_plans: dict = {}
+            layer.emit_fwd(self.fwd, self.pack_fwd)
         if need_backward:
             self._build_backward()
-        drop_dead_fp32_stores(getattr(self, "twinned", []))          # bf16 operand mode: see GeneratorEngine
+        drop_dead_fp32_stores(self.twinned)          # bf16 operand mode: see GeneratorEngine
 
     def _build_backward(self):
         ctx, b, pk, gr, B = self.ctx, self.bwd, self.pack_bwd, self.grads, self.B
@@ -365,61 +411,24 @@ class DiscriminatorEngine(_Engine):
                 ctx.keep.append(d)
                 plan.add("nirgan_conv_channel_dgrad", C.byref(d))
 
-    def input_plan(self, parts) -> Plan:
-        """parts: list of (NCHW tensor [nb, Cs, H, W], b0, c0) written straight into the halo'd input
-        (the torch.cat of model/pix2pix.py:197,202,216 never materialises)."""
-        key = tuple((t.data_ptr(), t.shape[0], t.shape[1], b0, c0) for t, b0, c0 in parts)
-        if key not in self._part_plans:
-            pl = Plan(self.ctx)
-            for t, b0, c0 in parts:
-                nb, cs = t.shape[0], t.shape[1]
-                assert t.is_contiguous() and t.shape[2] == self.H and t.shape[3] == self.W and b0 + nb <= self.B
-                dst = self.x4.ptr + b0 * self.x4.hp * self.x4.wp * 4 * 4
-                pl.add("nirgan_nchw_to_halo", t.data_ptr(), nb, cs, self.H, self.W, dst, 4, c0, 0, 1, L.BORDER_KEEP)
-            self._part_plans[key] = pl
-        return self._part_plans[key]
 
-    def forward(self, x: Optional[torch.Tensor] = None, parts=None, version: int = 0) -> torch.Tensor:
-        self.refresh_weights(version)
-        if parts is not None:
-            self.input_plan(parts).run()
-        else:
-            self.x_in.copy_(x)
-            self.in_plan.run()
-        self.fwd.run()
-        return self.out
-
-    def backward(self, dout: Optional[torch.Tensor], frozen: bool = False, version: int = 0, pred_only: bool = False) -> Optional[torch.Tensor]:
-        """frozen=False: parameter gradients.  frozen=True: gradient wrt the input ([B][H][W][4]), or wrt its
-        channel 3 only ([B][H][W]) when pred_only."""
-        self.refresh_weights(version, backward=True)
-        if dout is not None:
-            self.dout.copy_(dout)
-        if not frozen:
-            self.bwd.run()
-            return None
-        if pred_only:
-            self.bwd_pred.run()
-            return self.gpred
-        self.bwd_frozen.run()
-        return self.gx4.t
-
-
-class PixelDiscriminatorEngine:
+class PixelDiscriminatorEngine(_DiscriminatorFrontEnd):
     """PixelDiscriminator(input_nc=4, ndf=64, InstanceNorm): the 1x1 PatchGAN (model/networks.py:587-616) on the fused per-pixel
     kernels of csrc/pixdisc.hip, with the interface DiscriminatorEngine gives the trainer and the autograd bridge.
 
     ``precision`` ('fp32', 'bf16', 'bf16x3') is accepted for symmetry with the other engines; this network runs fp32 (fp32 MFMA) in
     every mode: its three contractions are 4, 64 and 128 deep and bound by the 20 bytes per pixel, not by the matrix pipe.
-    The whole gradient (8772 floats) is final only after the merge launch: there is no ``bwd_tail`` / ``bwd_mid`` bucket."""
+    The whole gradient (8772 floats) is final only after the merge launch: ``bwd_tail`` / ``bwd_mid`` stay None (no bucket).
+    The backward overwrites the flat gradient range and needs the statistics of this engine's last forward.  The kernels read the
+    parameters in place: the pack plans stay empty and ``refresh_weights`` launches nothing."""
 
     FLAT_ELEMS = 8772
 
     def __init__(self, params: Dict[str, torch.Tensor], grads: Optional[Dict[str, torch.Tensor]], B: int, H: int, W: int,
                  need_backward: bool = True, precision="fp32"):
         w1 = params["net.0.weight"]
-        self.ctx = ctx = Ctx(w1.device, precision)
-        self.params, self.grads, self.B, self.H, self.W = params, grads, B, H, W
+        super().__init__(params, grads, B, H, W, w1.device, precision)
+        ctx = self.ctx
         ndf, in_nc = w1.shape[0], w1.shape[1]
         if in_nc != 4 or ndf != 64:
             raise NotImplementedError("the pixel discriminator of the MI355X path is built for cat(rgb, nir) = 4 channels and ndf = 64")
@@ -430,8 +439,7 @@ class PixelDiscriminatorEngine:
         n_ws = int(L.backend().nirgan_pixdisc_ws_elems(B, H, W, ndf))
         if n_ws <= 0:
             raise ValueError(f"pixel discriminator: {B} x {H} x {W} is not a shape the kernels take (B*H*W < 2^31)")
-        self.x_in = ctx.zeros(B, 4, H, W)
-        self.x4 = Halo(ctx, B, H, W, 4, 0)
+        self._alloc_input(pad=0)
         self.stats = ctx.zeros(B, 2 * ndf, 2)
         self.out = ctx.zeros(B, 1, H, W)
         self.ws = ctx.zeros(n_ws)
@@ -443,11 +451,7 @@ class PixelDiscriminatorEngine:
             d.mode, d.ws, d.ws_elems = mode, self.ws.data_ptr(), n_ws
             ctx.keep.append(d)
             return d
-        self.fwd = Plan(ctx)
         self.fwd.add("nirgan_pixdisc_fwd", C.byref(desc()))
-        self.in_plan = Plan(ctx)
-        self.in_plan.add("nirgan_nchw_to_halo", self.x_in.data_ptr(), B, 4, H, W, self.x4.ptr, 4, 0, 0, 0, L.BORDER_KEEP)
-        self._part_plans: dict = {}
         if need_backward:
             assert grads is not None
             gbase = grads["net.0.weight"].data_ptr()
@@ -455,48 +459,10 @@ class PixelDiscriminatorEngine:
             self.dout = ctx.zeros(B, 1, H, W)
             self.gx4 = Halo(ctx, B, H, W, 4, 0)
             self.gpred = ctx.zeros(B, H, W)
-            self.bwd, self.bwd_frozen, self.bwd_pred = Plan(ctx), Plan(ctx), Plan(ctx)
+            self.bwd_frozen, self.bwd_pred = Plan(ctx), Plan(ctx)
             for plan, mode, gx in ((self.bwd, L.PIXDISC_PARAMS, None), (self.bwd_frozen, L.PIXDISC_INPUT, self.gx4.ptr),
                                    (self.bwd_pred, L.PIXDISC_PRED, self.gpred.data_ptr())):
                 d = desc(mode)
                 d.dout, d.gx = self.dout.data_ptr(), gx
                 d.grads = gbase if mode == L.PIXDISC_PARAMS else None
                 plan.add("nirgan_pixdisc_bwd", C.byref(d))
-
-    def input_plan(self, parts) -> Plan:
-        """parts: list of (NCHW tensor [nb, Cs, H, W], b0, c0) written straight into the [B][H][W][4] input
-        (the torch.cat of model/pix2pix.py:197,202,216 never materialises)."""
-        key = tuple((t.data_ptr(), t.shape[0], t.shape[1], b0, c0) for t, b0, c0 in parts)
-        if key not in self._part_plans:
-            pl = Plan(self.ctx)
-            for t, b0, c0 in parts:
-                nb, cs = t.shape[0], t.shape[1]
-                assert t.is_contiguous() and t.shape[2] == self.H and t.shape[3] == self.W and b0 + nb <= self.B
-                dst = self.x4.ptr + b0 * self.H * self.W * 4 * 4
-                pl.add("nirgan_nchw_to_halo", t.data_ptr(), nb, cs, self.H, self.W, dst, 4, c0, 0, 0, L.BORDER_KEEP)
-            self._part_plans[key] = pl
-        return self._part_plans[key]
-
-    def forward(self, x: Optional[torch.Tensor] = None, parts=None, version: int = 0) -> torch.Tensor:
-        """``version`` is accepted and unused: the kernels read the parameters in place, there is nothing to re-pack."""
-        if parts is not None:
-            self.input_plan(parts).run()
-        else:
-            self.x_in.copy_(x)
-            self.in_plan.run()
-        self.fwd.run()
-        return self.out
-
-    def backward(self, dout: Optional[torch.Tensor], frozen: bool = False, version: int = 0, pred_only: bool = False) -> Optional[torch.Tensor]:
-        """frozen=False: parameter gradients (the flat gradient range is overwritten).  frozen=True: gradient wrt the input
-        ([B][H][W][4]), or wrt its channel 3 only ([B][H][W]) when pred_only.  Needs the statistics of this engine's last forward."""
-        if dout is not None:
-            self.dout.copy_(dout)
-        if not frozen:
-            self.bwd.run()
-            return None
-        if pred_only:
-            self.bwd_pred.run()
-            return self.gpred
-        self.bwd_frozen.run()
-        return self.gx4.t

@@ -103,10 +103,10 @@ class _ShapeState:
         # data parallel, single part: three gradient buckets per network -- the tail of the flat gradient goes to RCCL from inside
         # the backward plan, as soon as the launches that complete it are on the stream (parallel.GradReducer.begin), the middle in
         # front of the first layer's backward; only the first layer's gradient (the head) follows after the plan.  With micro-batches the side parts are added after the plans: one bucket, after the join.
-        # The decision is per network: an engine without a ``bwd_tail`` (the pixel discriminator: 35 KB, final only after its merge
+        # The decision is per network: an engine whose ``bwd_tail`` is None (the pixel discriminator: 35 KB, final only after its merge
         # launch) goes as one blocking all-reduce while the generator keeps its buckets.
         self.bucketed = tr.reducer is not None and n == 1 and OPT.dp_buckets
-        self.bucketedD = self.bucketed and hasattr(self.micros[0].D2, "bwd_tail")
+        self.bucketedD = self.bucketed and self.micros[0].D2.bwd_tail is not None
         self.headD = self.headG = None
         if self.bucketed:
             m = self.micros[0]
@@ -130,7 +130,7 @@ class _ShapeState:
         tail = flat.grad[lo:hi]
         eng.bwd.insert_hook(index, lambda: tr.reducer.begin(tail))
         rest = [(0, lo), (hi, flat.total)]                 # what the tail leaves, as index ranges
-        mid = getattr(eng, "bwd_mid", None)
+        mid = eng.bwd_mid
         if mid is None:
             return [flat.grad[a:b] for a, b in rest if b > a]
         mindex, hfirst, hlast = mid

@@ -972,21 +972,16 @@ def test_conv_epilogue_leaves_the_instance_norm_partial_sums(case):
     the one produced with the separate statistics pass (OPT.epilogue_stats = False) to fp32 rounding; device against the numpy restatement
     too.  Stride-1, stride-2, and the four sub-pixel phases of a transposed convolution numbering their chunks into one workspace."""
     import os
-    from nirgan_hip.engine import ConvIN
+    from nirgan_hip.engine import ConvIN, LayerHost
     kind, B, H, W, Cin, Cout, k, s_ = case[:8]
 
-    class Eng:
-        pass
-
     def build(ctx, stats):
-        from nirgan_hip.engine import Weights, _Scratch, SlabPool
         from nirgan_hip.options import OPT
         OPT.epilogue_min_pixels = 0          # small layers too (the engines keep the separate pass below 16 K pixels)
         OPT.epilogue_stats = bool(stats)
         try:
             g = torch.Generator().manual_seed(5)
-            eng = Eng()
-            eng.ctx, eng.weights, eng.scratch, eng.slabs, eng.need_backward = ctx, Weights(ctx), _Scratch(ctx), SlabPool(ctx), False
+            eng = LayerHost(ctx, keep_wino_V=False)
             pad = k // 2 if kind == "rowpacked" else 1
             inp = Halo(ctx, B, H, W, Cin, pad)
             inp.t.copy_(torch.randn(inp.t.shape, generator=g).to(ctx.device))
@@ -1026,12 +1021,9 @@ def test_bf16_mode_stores_the_convolution_output_as_bf16(case):
     rounded to nearest-even bf16 -- bitwise the rounding of what the same launch stores as fp32 (OPT.bf16_y = False) -- while mean / rstd
     come from the fp32 accumulators (bitwise the same in both forms); the norm's apply and the two passes of its backward then use the
     rounded tensor: checked against torch on the widened values with the device's own statistics."""
-    from nirgan_hip.engine import ConvIN, SlabPool, Weights, _Scratch
+    from nirgan_hip.engine import ConvIN, LayerHost
     from nirgan_hip.options import OPT
     kind, B, H, W, Cin, Cout, k, s_ = case
-
-    class Eng:
-        pass
 
     def build(y16):
         OPT.bf16_y = y16
@@ -1039,8 +1031,7 @@ def test_bf16_mode_stores_the_convolution_output_as_bf16(case):
         try:
             ctx = Ctx(DEV, "bf16")
             g = torch.Generator().manual_seed(5)
-            eng = Eng()
-            eng.ctx, eng.weights, eng.scratch, eng.slabs, eng.need_backward = ctx, Weights(ctx), _Scratch(ctx), SlabPool(ctx), True
+            eng = LayerHost(ctx, keep_wino_V=True)
             inp_layer_out = Halo(ctx, B, H, W, Cin, 1, twin=True)
             x = torch.randn(inp_layer_out.t.shape, generator=g).to(DEV)
             inp_layer_out.t.copy_(x)
@@ -1487,19 +1478,15 @@ def test_producer_partial_sums_do_not_cancel_with_a_large_channel_mean(kind):
     """The instance-norm statistics a producer leaves (convolution epilogue / Winograd output transform: per chunk {k, sum (v - k),
     sum (v - k)^2, count} about a value of the chunk itself) for channels whose mean is ~1e3 times their spread: rstd from the merged
     chunks within 1e-4 of float64 (sums about the bias alone lose the variance entirely there: relative error ~1e-7 (mean / std)^2)."""
-    from nirgan_hip.engine import ConvIN, Weights, _Scratch, SlabPool
+    from nirgan_hip.engine import ConvIN, LayerHost
     from nirgan_hip.options import OPT
     B, H, W, Cin, Cout = (16 if kind == "conv" else 2), 64, 64, 128, 128        # (the direct tile splits K below ~400 tiles: no epilogue sums then)
     g = torch.Generator().manual_seed(77)
-
-    class Eng:
-        pass
     OPT.epilogue_min_pixels = 0
     OPT.winograd = "f6" if kind == "wino6" else "off"
     try:
         ctx = Ctx(DEV, "fp32")
-        eng = Eng()
-        eng.ctx, eng.weights, eng.scratch, eng.slabs, eng.need_backward = ctx, Weights(ctx), _Scratch(ctx), SlabPool(ctx), False
+        eng = LayerHost(ctx, keep_wino_V=False)
         inp = Halo(ctx, B, H, W, Cin, 1)
         # a constant per input channel plus a small texture: every output channel gets a large mean (sum of w * const) and a small spread
         x = 5.0 + 0.01 * torch.randn(inp.t.shape, generator=g)
