@@ -924,6 +924,41 @@ int nirgan_param_scale_bwd(const float* gout, const float* x, const float* param
 int nirgan_fill(float* dst, int64_t n, float value, void* stream);
 int nirgan_axpy(float* y, const float* x, int64_t n, float alpha, void* stream);   /* y += alpha*x */
 
+/* ---------------------------------------------------------------------------------------
+ * Dropout of the generator's residual blocks (model/networks.py:415-416: nn.Dropout(0.5) behind the first InstanceNorm + ReLU of a
+ * ResnetBlock) as a COUNTER-BASED mask: no mask tensor is stored, forward and backward compute the same bits again.
+ *
+ * Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with
+ *     key     = (seed_lo, seed_hi)
+ *     counter = (q_lo, q_hi, stream_id, call)
+ *     q       = (((sample0 + b) * H + h) * W + w) * (C / 4) + c / 4      -- the channel-quad index of the LOGICAL, un-padded tensor, 64 bits
+ * The four output words belong to channels 4 (c / 4) + 0 .. 3; an element is kept iff the top bit of its word is 1 (p = 0.5, the only
+ * rate the reference can reach), and
+ *     out = keep ? 2.0f * x : 0.0f
+ * a select, not a product: a dropped NaN or Inf becomes +0; the multiplication by 2 is exact.
+ *
+ * state: uint32_t[4] = {seed_lo, seed_hi, call, 0} in DEVICE memory, read by the kernels (plans stay static and graph-capturable).
+ * The advance entry sets call += 1 on the stream (one thread, a vector store); the forward plan of a network runs it first, and the
+ * backward plan reads the call the forward left.
+ *
+ * The halo entry works IN PLACE on a halo'd NHWC buffer [B][H + 2 pad][W + 2 pad][C]: every element of the padded grid is replaced by
+ * the select above with the mask of its REFLECTED SOURCE PIXEL (ReflectionPad2d index rule).  On an activation whose halo is a
+ * reflection the result is again the reflection of the masked interior; on a gradient over the padded grid, fold(g * m_pad) =
+ * fold(g) * m, so the instance norm's backward with g_fold = 1 that follows needs no change.  pad = 0: a dense tensor.
+ * One thread per channel quad (16-byte loads and stores), grid-stride, 64-bit indexing; deterministic, no atomics.
+ * Argument errors (null pointer, a non-positive extent, C % 4 != 0, pad < 0, pad >= min(H, W), sample0 < 0, buf not 16-byte aligned,
+ * buf_elems below B (H + 2 pad)(W + 2 pad) C, that count at 2^40 or more) return NIRGAN_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    float* buf; int64_t buf_elems;        /* the halo'd buffer and its size in floats */
+    int B, H, W, C, pad;
+    const uint32_t* state;                /* device: {seed_lo, seed_hi, call, 0} */
+    uint32_t stream_id;                   /* which mask of the call: the residual block's index */
+    int sample0;                          /* index of this buffer's first sample in the logical batch (micro-batches) */
+} nirgan_dropout_desc;
+int nirgan_dropout_advance(uint32_t* state, void* stream);
+int nirgan_dropout_halo(const nirgan_dropout_desc* d, void* stream);
+
 /* run a pre-built list of descriptors back to back (one host call per phase) */
 #define NIRGAN_OP_CONV 1
 #define NIRGAN_OP_WGRAD 2

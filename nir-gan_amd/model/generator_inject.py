@@ -33,6 +33,7 @@ class ResnetGenerator_inject(_HipNet):
         if self.inject_style == "add" and not self.scaling_param:
             raise AttributeError("inject style 'add' reads scale_param (generator_inject.py:123); enable scaling_param")
         self.n_blocks, self.data_pad = n_blocks, 0
+        self.use_dropout = not base.no_dropout
         model = _resnet_sequence(base.input_nc, base.output_nc, base.ngf, norm_layer, not base.no_dropout, n_blocks, 'reflect')
         self.embed_fc_ou_square = 128
         self.fc = Linear(in_features=256, out_features=self.embed_fc_ou_square * self.embed_fc_ou_square)
@@ -45,11 +46,11 @@ class ResnetGenerator_inject(_HipNet):
         self.model = nn.Sequential(*model)
 
     def _make_engine(self, key):
-        B, H, W, pad, need_bwd = key
+        B, H, W, pad, need_bwd, drop = key if len(key) == 6 else key + (False,)      # (the active-dropout bit: functional.GeneratorFn)
         f = self._flat()
         cfg = {"style": self.inject_style, "use_scale": bool(self.scaling_param), "post_correction": bool(self.post_correction)}
         return GeneratorEngine(f.param_views(), f.grad_views(), self.n_blocks, B, H, W, data_pad=pad, inject=cfg,
-                               need_backward=need_bwd, precision=getattr(self, "precision", "fp32"))
+                               need_backward=need_bwd, precision=getattr(self, "precision", "fp32"), dropout=drop)
 
     def forward(self, input, embeds):
         return HF.GeneratorFn.apply(self, torch.is_grad_enabled(), input, embeds, *self.parameters())

@@ -8,8 +8,9 @@ are parameter containers: ``forward`` runs the hand-written HIP engines of ``nir
 (there is no torch.nn compute and no CPU fallback).
 
 Supported on this path: ``netG`` resnet_6blocks / resnet_9blocks, ``netD`` basic / n_layers(3) / pixel (ndf 64, fp32 in
-every operand mode), ``norm='instance'``, no dropout, ``gan_mode`` lsgan / vanilla / wgangp -- everything the shipped configs select
-(configs/config_px2px.yaml:13-21) and all three objectives of the reference's ``GANLoss``, each one fused HIP pass (``nirgan_lsgan``,
+every operand mode), ``norm='instance'``, ``use_dropout`` (the reference's ``not opt.no_dropout``: nn.Dropout(0.5) in every ResnetBlock, a
+counter-based mask recomputed in the backward -- ``set_dropout_state`` / ``dropout_state`` below; fp32 operand mode only),
+``gan_mode`` lsgan / vanilla / wgangp -- everything the shipped configs select (configs/config_px2px.yaml:13-21) and all three objectives of the reference's ``GANLoss``, each one fused HIP pass (``nirgan_lsgan``,
 ``nirgan_gan_loss``).  ``cal_gradient_penalty`` is not here (no caller, and it needs a double backward).  Other names the reference
 knows raise NotImplementedError.
 """
@@ -22,6 +23,7 @@ import torch
 import torch.nn as nn
 from torch.nn import init
 
+from nirgan_hip import dropout as HD
 from nirgan_hip import functional as HF
 from nirgan_hip import lib as L
 from nirgan_hip.flat import FlatParams
@@ -156,19 +158,62 @@ class _HipNet(nn.Module):
             self.__dict__["_pool_obj"] = p
         return p
 
+    # ---- dropout of the residual blocks (generators built with use_dropout=True; nirgan_hip/dropout.py)
+    use_dropout = False
+
+    def dropout_active(self) -> bool:
+        """nn.Dropout's own rule: the module drops in training mode only; ``eval()`` gives the identity (the engines without dropout)."""
+        return bool(self.use_dropout and self.training)
+
+    def set_dropout_state(self, seed=None, call=None):
+        """Pin the mask sequence: ``seed`` (an integer, taken mod 2^64) keys the generator, ``call`` is the number of training forwards
+        already counted -- the next one runs as call + 1.  None leaves a value as it is.  Not part of the reference's API."""
+        if seed is not None:
+            self.__dict__["_drop_seed"] = int(seed) & HD.MASK64
+        if call is not None:
+            self.__dict__["_drop_call"] = int(call) & 0xFFFFFFFF
+
+    def dropout_state(self):
+        """(seed, call) of the LAST training forward, as ``nirgan_hip.dropout.mask`` takes them: the seed as the kernels see it (with the
+        rank folded in under torch.distributed; None until the first training forward has drawn it), and the forwards counted so far.
+        ``call`` is not written to checkpoints: a resumed run restarts the mask sequence (set it with ``set_dropout_state``)."""
+        seed = self.__dict__.get("_drop_seed")
+        return (None if seed is None else self._dropout_seed()), self.__dict__.get("_drop_call", 0)
+
+    def _dropout_seed(self) -> int:
+        """The key of this rank's masks.  The default is drawn from torch's default generator at the FIRST training forward (construction
+        consumes no random numbers beyond the reference's initialisation), so ``torch.manual_seed`` fixes it."""
+        seed = self.__dict__.get("_drop_seed")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            self.__dict__["_drop_seed"] = seed
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            seed ^= (dist.get_rank() * HD.RANK_STRIDE) & HD.MASK64
+        return seed
+
+    def _dropout_begin(self, engines) -> None:
+        """In front of a training forward: every engine that takes part gets (seed, call) -- a host-to-device copy only when its words
+        differ (another engine ran the previous forward, or the state was set by hand) -- and the module counts the forward."""
+        seed, call = self._dropout_seed(), self.__dict__.get("_drop_call", 0)
+        for eng in engines:
+            eng.set_dropout_state(seed, call)
+        self.__dict__["_drop_call"] = (call + 1) & 0xFFFFFFFF
+
 
 class ResnetBlock(nn.Module):
-    """Parameter layout of the reference ResnetBlock (networks.py:377-434): conv_block.1 / conv_block.5."""
+    """Parameter layout of the reference ResnetBlock (networks.py:377-434): conv_block.1 / conv_block.5, or conv_block.1 / conv_block.6
+    with use_dropout (the nn.Dropout(0.5) is entry 4; it owns no parameters and the initialisation order is unchanged)."""
 
     def __init__(self, dim, padding_type, norm_layer, use_dropout, use_bias):
         super().__init__()
         if padding_type != 'reflect':
             raise NotImplementedError('padding [%s] is not implemented on the MI355X path' % padding_type)
+        block = [nn.ReflectionPad2d(1), Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim), nn.ReLU(True)]
         if use_dropout:
-            raise NotImplementedError('dropout is not on the MI355X path (no shipped config enables it)')
-        self.conv_block = nn.Sequential(
-            nn.ReflectionPad2d(1), Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim), nn.ReLU(True),
-            nn.ReflectionPad2d(1), Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim))
+            block += [nn.Dropout(0.5)]
+        block += [nn.ReflectionPad2d(1), Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim)]
+        self.conv_block = nn.Sequential(*block)
 
 
 def _resnet_sequence(input_nc, output_nc, ngf, norm_layer, use_dropout, n_blocks, padding_type):
@@ -200,13 +245,14 @@ class ResnetGenerator(_HipNet):
         if output_nc != 1 or input_nc > 4 or ngf % 4:
             raise NotImplementedError('the MI355X path covers RGB(+1) -> 1 band with ngf % 4 == 0')
         self.n_blocks, self.data_pad = n_blocks, 0
+        self.use_dropout = bool(use_dropout)
         self.model = nn.Sequential(*_resnet_sequence(input_nc, output_nc, ngf, norm_layer, use_dropout, n_blocks, padding_type))
 
     def _make_engine(self, key):
-        B, H, W, pad, need_bwd = key
+        B, H, W, pad, need_bwd, drop = key if len(key) == 6 else key + (False,)      # (the active-dropout bit: functional.GeneratorFn)
         f = self._flat()
         return GeneratorEngine(f.param_views(), f.grad_views(), self.n_blocks, B, H, W, data_pad=pad, need_backward=need_bwd,
-                               precision=getattr(self, "precision", "fp32"))
+                               precision=getattr(self, "precision", "fp32"), dropout=drop)
 
     def forward(self, input):
         return HF.GeneratorFn.apply(self, torch.is_grad_enabled(), input, None, *self.parameters())

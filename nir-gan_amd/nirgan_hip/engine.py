@@ -1008,6 +1008,10 @@ class ConvIN:
         self.keep_z = keep_z   # inject: `out` holds z (no act); the modulation produces the activated tensor
         self.producer, self.defer_apply = None, False       # fold_producer_apply: the consumer's link / the producer's "statistics only"
         self.wino6, self.wino_fwd, self.wino_fwd_keeps_V = False, None, False       # emit_fwd: Winograd layer, its descriptor, V resident
+        # set by the network when something rewrites the gradient wrt `out` between its producer and this layer's backward (dropout: the
+        # mask lands on the padded gradient buffer): the backward then reads that buffer with the two-pass nirgan_instnorm_bwd -- no first
+        # pass inside the producer's output transform (fuse_gz) or convolution epilogues, no dY evaluated inside the transform (fuse_dy_norm)
+        self.two_pass_in_bwd = False
 
     def fold_producer_apply(self, producer: "ConvIN"):
         """`producer.out` has this layer as its ONE reader: InstanceNorm + activation + reflect pad of the producer move into this layer's
@@ -1131,11 +1135,12 @@ class ConvIN:
                   and wino_dgrad_applicable(ctx, k, s, dgrad_out, self.cout, inp.C) and inp.C > 64
                   and inp.pad == 1 and p == 1 and self.cout % 128 == 0)
         fuse_dy = (w6_bwd and k == 3 and self.norm and dy.t16 is None and OPT.fuse_dy_norm and wino6_variant(3) == 6
-                   and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU))
+                   and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU) and not self.two_pass_in_bwd)
         # the instance norm's backward: its first pass inside the launch that produced g where that launch can take it
         scratch = eng.scratch.get()
-        pre_sums, ws, gsum = (self._first_pass_from_w6_output(g, g_fold, g2, gsum, act)
-                              or self._first_pass_from_conv_epilogues(g, g_fold, g2, gsum, act) or (0, scratch, gsum))
+        fused_first = None if self.two_pass_in_bwd else (self._first_pass_from_w6_output(g, g_fold, g2, gsum, act)
+                                                         or self._first_pass_from_conv_epilogues(g, g_fold, g2, gsum, act))
+        pre_sums, ws, gsum = fused_first or (0, scratch, gsum)
         nd = emit_in_bwd(plan, ctx, g=g, g_fold=g_fold, g2=g2, act=act, y=self.y, stats=self.stats, norm=self.norm, dy=self.dy, gsum=gsum,
                          dbias=(None if self.norm else gb),   # a bias in front of InstanceNorm has gradient exactly 0: left at 0
                          ws=ws, shape=(inp.B, self.OH, self.OW, self.cout), pre_sums=pre_sums, sums_only=fuse_dy)

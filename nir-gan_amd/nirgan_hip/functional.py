@@ -89,7 +89,10 @@ class GeneratorFn(torch.autograd.Function):
         # optimizer pass of the batch does not repeat it; inference (no_grad / eval): a forward-only engine without backward buffers
         need_bwd = wants or (grad_mode and net.training)
         ver = net._flat().values_version()
-        key = (B, H, W, net.data_pad, need_bwd)
+        # dropout (a generator built with use_dropout, in training mode): its own engines, and every forward draws the next mask as the
+        # reference's nn.Dropout does -- the repeated forward of a batch is NOT the first one again, so nothing is remembered
+        drop = bool(getattr(net, "use_dropout", False) and net.training)
+        key = (B, H, W, net.data_pad, need_bwd) + ((True,) if drop else ())      # the active bit: engines with and without dropout never mix
         rec = net.__dict__.get("_fwd_record")
         net.__dict__["_fwd_record"] = None
         if rec is not None and need_bwd and rec.matches(rgb, embeds, ver, key):
@@ -98,9 +101,11 @@ class GeneratorFn(torch.autograd.Function):
         else:
             rec = None
             lease = net._pool().lease(key)
+            if drop:
+                net._dropout_begin([lease.eng])
             lease.eng.forward(rgb.detach().contiguous().float(), None if embeds is None else embeds.detach().contiguous().float(), version=ver)
         out = lease.eng.pred.clone()
-        if need_bwd:
+        if need_bwd and not drop:
             net.__dict__["_fwd_record"] = rec if rec is not None else _ForwardRecord(rgb, embeds, ver, key, lease)
         if wants:
             lease.bound = True

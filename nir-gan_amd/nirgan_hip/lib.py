@@ -124,6 +124,11 @@ class InjectBwdDesc(C.Structure):
                 ("dz", fp), ("de", fp), ("dscale", fp), ("ws", fp), ("ws_elems", i64)]
 
 
+class DropoutDesc(C.Structure):
+    _fields_ = [("buf", fp), ("buf_elems", i64), ("B", i32), ("H", i32), ("W", i32), ("C", i32), ("pad", i32),
+                ("state", fp), ("stream_id", C.c_uint32), ("sample0", i32)]
+
+
 class MetricsDesc(C.Structure):
     _fields_ = [("pred", fp), ("target", fp), ("planes", i32), ("H", i32), ("W", i32),
                 ("window", i32), ("sigma", f32), ("max_val", f32), ("eps", f32),
@@ -342,6 +347,8 @@ PROTOTYPES = {
     "nirgan_bilinear_bwd": (i32, [fp, i32, i32, i32, fp, i32, i32, fp]),
     "nirgan_inject_fwd": (i32, [C.POINTER(InjectFwdDesc), fp]),
     "nirgan_inject_bwd": (i32, [C.POINTER(InjectBwdDesc), fp]),
+    "nirgan_dropout_advance": (i32, [fp, fp]),
+    "nirgan_dropout_halo": (i32, [C.POINTER(DropoutDesc), fp]),
     "nirgan_param_scale_fwd": (i32, [fp, fp, fp, i64, fp]),
     "nirgan_param_scale_bwd": (i32, [fp, fp, fp, fp, fp, fp, i64, i64, fp]),
     "nirgan_colsum": (i32, [fp, i64, i32, fp, i32, fp]),

@@ -16,6 +16,7 @@ import torch
 from . import geometry as G
 from . import lib as L
 from .options import OPT
+from .dropout import split_seed, state_words
 from .engine import (ConvIN, Ctx, Halo, LayerHost, Plan, TapPlaneConv, drop_dead_fp32_stores, emit_conv, grad_halo,
                      emit_deferred_reduce_rows, emit_w6_deferred_finishes, emit_wgrad, wino_applicable)
 
@@ -50,13 +51,23 @@ class _Engine(LayerHost):
 
 
 class GeneratorEngine(_Engine):
-    """ResnetGenerator(input_nc=3, output_nc=1, ngf, n_blocks, InstanceNorm, reflect padding)."""
+    """ResnetGenerator(input_nc=3, output_nc=1, ngf, n_blocks, InstanceNorm, reflect padding).
+
+    dropout=True: nn.Dropout(0.5) ACTIVE behind the first InstanceNorm + ReLU of every residual block (model/networks.py:415-416), as the
+    counter-based mask of csrc/dropout.hip.  `drop_state` holds {seed_lo, seed_hi, call, 0} on the device: the forward plan
+    advances `call` first, block j masks c1's materialised output with stream_id = j, the backward plan masks the padded gradient c2's
+    data gradient leaves with the same words.  sample0: index of this engine's first sample in the logical batch (micro-batches).
+    dropout=False (an eval-mode net, a net built without dropout) emits exactly the plans it always did."""
 
     def __init__(self, params: Dict[str, torch.Tensor], grads: Optional[Dict[str, torch.Tensor]], n_blocks: int,
                  B: int, H: int, W: int, data_pad: int = 0, inject: Optional[dict] = None, need_backward: bool = True,
-                 precision="fp32"):
+                 precision="fp32", dropout: bool = False, sample0: int = 0):
         dev = params["model.1.weight"].device
         super().__init__(dev, precision, keep_wino_V=need_backward)
+        self.dropout, self.sample0 = bool(dropout), int(sample0)
+        if self.dropout and self.ctx.precision != 0:
+            raise NotImplementedError("dropout runs with precision='fp32' only: the bf16 operand modes keep bf16 twins of the buffers the "
+                                      "mask is applied to")
         ctx = self.ctx
         self.params, self.grads = params, grads
         self.n_blocks, self.B, self.H, self.W, self.data_pad = n_blocks, B, H, W, data_pad
@@ -96,15 +107,22 @@ class GeneratorEngine(_Engine):
                          out_pad=1, out_border=last_border)
         self.blocks = []
         u = self.L3.out
+        # a net built with dropout carries the block's second convolution as conv_block.6 (the nn.Dropout is entry 4): read off the keys, so
+        # that an eval-mode engine of such a net is this same code
+        self.c2_key = {i: ("conv_block.6" if f"model.{i}.conv_block.6.weight" in params else "conv_block.5") for i in lay["blocks"]}
         for j, i in enumerate(lay["blocks"]):
+            k2 = self.c2_key[i]
             c1 = ConvIN(self, f"b{j}c1", "conv", u, P(i, "conv_block.1.weight"), P(i, "conv_block.1.bias"), k=3, s=1, p=1,
                         cout=4 * ngf, out_pad=1, out_border=L.BORDER_REFLECT)
-            c2 = ConvIN(self, f"b{j}c2", "conv", c1.out, P(i, "conv_block.5.weight"), P(i, "conv_block.5.bias"), k=3, s=1, p=1,
+            c2 = ConvIN(self, f"b{j}c2", "conv", c1.out, P(i, k2 + ".weight"), P(i, k2 + ".bias"), k=3, s=1, p=1,
                         cout=4 * ngf, act=L.ACT_NONE, residual=u, out_pad=1,
                         out_border=L.BORDER_REFLECT if j < n_blocks - 1 else L.BORDER_KEEP)
             # c1's normalised output has ONE reader, c2's Winograd input transform: fold InstanceNorm + ReLU + reflect pad into that
             # transform and never write the buffer.  Needs c2's V kept for its weight gradient (else the backward re-reads c1.out).
-            if wino_applicable(self.ctx, c2.inp, 3, 1, 1, c2.cout, c2.OH, c2.OW) and OPT.fold_apply:
+            # (dropout: the mask is applied to the materialised buffer, and c1's backward reads a gradient the mask has rewritten)
+            if self.dropout:
+                c1.two_pass_in_bwd = True
+            elif wino_applicable(self.ctx, c2.inp, 3, 1, 1, c2.cout, c2.OH, c2.OW) and OPT.fold_apply:
                 c2.fold_producer_apply(c1)
             self.blocks.append((i, c1, c2))
             u = c2.out
@@ -124,14 +142,21 @@ class GeneratorEngine(_Engine):
 
         # ---------------- forward plan
         f, pk = self.fwd, self.pack_fwd
+        if self.dropout:
+            self.drop_state = state_words(0, 0).to(dev)          # {seed_lo, seed_hi, call, 0}: set_dropout_state
+            self.drop_words = (0, 0, 0)                          # host mirror of the first three words (no read-back in the steady state)
+            ctx.keep.append(self.drop_state)
+            f.add("nirgan_dropout_advance", self.drop_state.data_ptr())
         f.add("nirgan_nchw_to_halo", self.rgb_in.data_ptr(), B, in_nc, H, W, self.x4.ptr, 4, 0, data_pad, 3, L.BORDER_REFLECT)
         self.L1.emit_fwd(f, pk)
         self.L2.emit_fwd(f, pk)
         if inject is not None:
             self._emit_inject_fwd(f)
         self.L3.emit_fwd(f, pk)
-        for _, c1, c2 in self.blocks:
+        for j, (_, c1, c2) in enumerate(self.blocks):
             c1.emit_fwd(f, pk)
+            if self.dropout:
+                self._emit_dropout(f, c1.out, j)
             c2.emit_fwd(f, pk)
         self.U1.emit_fwd(f, pk)
         self.U2.emit_fwd(f, pk)
@@ -142,6 +167,25 @@ class GeneratorEngine(_Engine):
             self._build_backward()
         # bf16 operand mode: activations / output gradients that every reader takes from the bf16 twin are stored as bf16 only
         drop_dead_fp32_stores(self.twinned)
+
+    # ------------------------------------------------------------------ dropout
+    def _emit_dropout(self, plan: Plan, buf: Halo, stream_id: int):
+        """The mask of residual block `stream_id` in place on a halo'd buffer of the trunk's geometry: c1's output (forward) or the padded
+        gradient wrt it (backward) -- every halo element takes the mask of the pixel it reflects (include/nirgan_hip.h)."""
+        d = L.DropoutDesc()
+        d.buf, d.buf_elems = buf.ptr, buf.elems
+        d.B, d.H, d.W, d.C, d.pad = buf.B, buf.H, buf.W, buf.C, buf.pad
+        d.state, d.stream_id, d.sample0 = self.drop_state.data_ptr(), stream_id, self.sample0
+        self.ctx.keep.append(d)
+        plan.add("nirgan_dropout_halo", C.byref(d))
+
+    def set_dropout_state(self, seed, call: int) -> None:
+        """Write {seed, call} into the device state (the next forward runs as call + 1); a no-op when the words are already there."""
+        lo, hi = split_seed(seed)
+        words = (lo, hi, int(call) & 0xFFFFFFFF)
+        if words != self.drop_words:
+            self.drop_state.copy_(state_words((lo, hi), call))
+            self.drop_words = words
 
     # ------------------------------------------------------------------ SatCLIP injection
     def _emit_inject_fwd(self, f: Plan):
@@ -238,8 +282,11 @@ class GeneratorEngine(_Engine):
             else:
                 gsum, skip_next = dense[flip], dense[flip]
                 flip ^= 1
-            c2.emit_bwd(b, pk, g=g_in, g_fold=g_fold, g2=g_skip, gsum=gsum, gw=GW(i, "conv_block.5.weight"),
-                        gb=GW(i, "conv_block.5.bias"), dgrad_out=gq, act=L.ACT_NONE)
+            k2 = self.c2_key[i]
+            c2.emit_bwd(b, pk, g=g_in, g_fold=g_fold, g2=g_skip, gsum=gsum, gw=GW(i, k2 + ".weight"),
+                        gb=GW(i, k2 + ".bias"), dgrad_out=gq, act=L.ACT_NONE)
+            if self.dropout:         # the mask of the forward (same stream id, the call the forward left) on the padded gradient: fold(g m_pad) = fold(g) m
+                self._emit_dropout(b, gq, j)
             c1.emit_bwd(b, pk, g=gq, g_fold=True, gw=GW(i, "conv_block.1.weight"), gb=GW(i, "conv_block.1.bias"), dgrad_out=gp)
             g_in, g_fold, g_skip = gp, True, skip_next
         emit_w6_deferred_finishes(b, ctx)         # the blocks' Winograd weight gradients: one inverse-transform launch for all of them
@@ -270,6 +317,9 @@ class GeneratorEngine(_Engine):
         if self.inject is not None:
             self.emb_in.t.view(self.B, 256).copy_(embeds)
         self.fwd.run()
+        if self.dropout:
+            lo, hi, call = self.drop_words
+            self.drop_words = (lo, hi, (call + 1) & 0xFFFFFFFF)       # what nirgan_dropout_advance just did on the device
         return self.pred
 
     def backward(self, dpred: Optional[torch.Tensor], version: int = 0) -> None:

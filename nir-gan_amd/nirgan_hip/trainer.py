@@ -14,7 +14,8 @@ GAN is the objective of ``gan_mode``: MSE against the label (lsgan, nirgan_lsgan
 
 Differences from the reference that do not change results: the generator forward runs once
 (its parameters do not change between the two optimizer passes, so the second forward would
-reproduce ``pred`` bit for bit); the fake and real PatchGAN passes of the D step run as one
+reproduce ``pred`` bit for bit -- with dropout the reference's second forward draws a second
+mask; here both passes of a batch see the ONE mask of the one forward); the fake and real PatchGAN passes of the D step run as one
 batch of 2B (InstanceNorm is per sample); torch.cat never materialises.  Optionally
 (``micro_batches=2``) the batch is cut into parts that run concurrently on separate HIP streams.
 """
@@ -41,7 +42,9 @@ class _Micro:
         B = hi - lo
         self.lo, self.hi, self.B, self.scale = lo, hi, B, scale
         gp, dp = tr.flatG.param_views(), tr.flatD.param_views()
-        self.G = GeneratorEngine(gp, gradG, tr.n_blocks, B, H, W, data_pad=tr.padding, inject=tr.inject, precision=tr.precision)
+        # (dropout: the micro-batch's masks are those of samples lo .. hi - 1 of the whole batch)
+        self.G = GeneratorEngine(gp, gradG, tr.n_blocks, B, H, W, data_pad=tr.padding, inject=tr.inject, precision=tr.precision,
+                                 dropout=tr.dropout, sample0=lo if tr.dropout else 0)
         d_engine = getattr(tr.netD, "engine_class", DiscriminatorEngine)       # netD 'pixel': nets.PixelDiscriminatorEngine
         self.D2 = d_engine(dp, gradD, 2 * B, H, W, precision=tr.precision)
         self.D1 = d_engine(dp, gradD, B, H, W, precision=tr.precision)
@@ -189,6 +192,7 @@ class Pix2PixTrainer:
         self.micro_batches = int(micro_batches)   # parts of the batch run on separate HIP streams (1 = off)
         self._states: Dict[tuple, _ShapeState] = {}
         self._shape = None
+        self.dropout = False              # the generator's dropout is active (netG.use_dropout and netG.training): read from netG per step
         self.losses = None
         self.steps = 0
         self._synced_ptrs = None
@@ -219,9 +223,12 @@ class Pix2PixTrainer:
         if self.losses is None or rebuilt:
             # 0 D_fake 1 D_real 2 G_gan 3.. pix sums[7] 10 weighted SSIM term
             self.losses = torch.zeros(16, dtype=torch.float32, device=self.flatG.flat.device)
-        st = self._states.get((B, H, W))
+        active = getattr(self.netG, "dropout_active", None)
+        self.dropout = bool(active()) if active is not None else False
+        key = (B, H, W) + ((True,) if self.dropout else ())        # the active bit, as in the generator's engine pool (functional.GeneratorFn)
+        st = self._states.get(key)
         if st is None:
-            st = self._states[(B, H, W)] = _ShapeState(self, B, H, W)
+            st = self._states[key] = _ShapeState(self, B, H, W)
         self._shape = (B, H, W)
         self._state = st
         m0 = st.micros[0]                 # single-part view (tests, probes): the first micro-batch's engines
@@ -301,6 +308,8 @@ class Pix2PixTrainer:
             m.rgb.copy_(rgb[m.lo:m.hi])
             m.nir.copy_(nir[m.lo:m.hi])
         L.check(L.backend().nirgan_fill(self.losses.data_ptr(), 16, 0.0, st), "fill")
+        if self.dropout:      # ONE generator forward per batch: both optimizer passes see the mask of this call (all micro-batches the same call)
+            self.netG._dropout_begin([m.G for m in state.micros])
         # ---- optimizer 0: generator forward + discriminator on [fake ; real], per micro-batch
         self._fork(state)
         for m, s in zip(state.micros, state.streams):
