@@ -875,8 +875,12 @@ class EmuBackend:
     def nirgan_hist_match(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("hist_match")
+        if not (d.image and d.reference and d.out and d.ws):
+            return self._fail("hist_match: null pointer")
         if d.ws_bytes < self.nirgan_hist_match_ws_bytes(d.B, d.N):
             return self._fail("hist_match: workspace too small")
+        if int(d.ws) & 7:
+            return self._fail("hist_match: workspace must be 8-byte aligned")
         img = arr(d.image, d.B * d.N).reshape(d.B, d.N)
         tmp = arr(d.reference, d.B * d.N).reshape(d.B, d.N)
         out = arr(d.out, d.B * d.N).reshape(d.B, d.N)
@@ -894,6 +898,8 @@ class EmuBackend:
     def nirgan_image_metrics(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("metrics")
+        if not (d.pred and d.target and d.ws and d.means):
+            return self._fail("image_metrics: null pointer")
         r = d.window // 2
         if d.window % 2 == 0 or d.window > 11 or d.H <= r or d.W <= r:
             return self._fail("image_metrics: bad window")
@@ -927,6 +933,8 @@ class EmuBackend:
     def nirgan_ssim_loss(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("ssim_loss")
+        if not (d.pred and d.target and d.ws):
+            return self._fail("ssim_loss: null pointer")
         r = d.window // 2
         if d.window % 2 == 0 or d.window > 11 or d.H <= r or d.W <= r:
             return self._fail("ssim_loss: bad window")
@@ -964,21 +972,28 @@ class EmuBackend:
     def nirgan_emd_loss(self, ref, stream=None):
         d = obj(ref)
         self.calls.append("emd_loss")
+        if not (d.pred and d.target and d.ws):
+            return self._fail("emd_loss: null pointer")
         if d.B <= 0 or d.N <= 0 or d.N >= 1 << 24:
             return self._fail("emd_loss: out of range")
         if d.ws_bytes < self.nirgan_emd_loss_ws_bytes(d.B, d.N, bool(d.grad_pred)):
             return self._fail("emd_loss: workspace too small")
+        if int(d.ws) & 7:
+            return self._fail("emd_loss: workspace must be 8-byte aligned")
         n = d.B * d.N
-        with torch.enable_grad():
-            a = torch.from_numpy(arr(d.pred, n).reshape(d.B, d.N).astype(np.float64)).requires_grad_(True)
-            b = torch.from_numpy(arr(d.target, n).reshape(d.B, d.N).astype(np.float64))
-            v = (torch.cumsum(torch.softmax(a, 1), 1) - torch.cumsum(torch.softmax(b, 1), 1)).abs().mean()
-            g = torch.autograd.grad(v, a)[0] if d.grad_pred else None
+        a = torch.from_numpy(arr(d.pred, n).reshape(d.B, d.N).astype(np.float64))
+        b = torch.from_numpy(arr(d.target, n).reshape(d.B, d.N).astype(np.float64))
+        p = torch.softmax(a, 1)
+        # the header: the reference compares fp32 CDFs (torch.cumsum returns float32), so the sign of a difference is the rounded one's
+        diff = torch.cumsum(p, 1).float().double() - torch.cumsum(torch.softmax(b, 1), 1).float().double()
+        v = diff.abs().mean()
         if d.value:
             arr(d.value, 1)[0] = v.item()
         if d.loss:
             arr(d.loss, 1)[0] += d.weight * v.item()
         if d.grad_pred:
+            g = torch.sign(diff).flip(1).cumsum(1).flip(1)
+            g = p * (g - (p * g).sum(1, keepdim=True)) / n
             arr(d.grad_pred, n)[:] += (d.weight * g).reshape(-1).numpy().astype(np.float32)
         return 0
 
