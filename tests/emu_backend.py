@@ -595,6 +595,11 @@ class EmuBackend:
         if v not in (3, 6):
             return self._fail("wino6_input_norm: 3x3 filters only")
         B, H, W, Cc = d.B, d.H, d.W, d.C
+        if Cc % 4 or min(B, H - 1, W - 1, Cc) <= 0:
+            return self._fail("wino6_input: bad shape")
+        n = self._geo6(v)[2]
+        if d.V_elems < n * n * self.nirgan_wino6_tiles_r(B, H, W, v) * Cc:
+            return self._fail("wino6_input: V workspace too small")
         yv = arr(y, B * H * W * Cc).reshape(B, H, W, Cc)
         m, r = arr(mean, B * Cc).reshape(B, 1, 1, Cc), arr(rstd, B * Cc).reshape(B, 1, 1, Cc)
         a = self._act(((yv - m) * r).astype(np.float32).astype(np.float64), act, slope).astype(np.float32)       # in_apply's fp32 arithmetic
@@ -608,6 +613,10 @@ class EmuBackend:
         self.calls.append("wino6_gemm")
         if d.algo not in W6_ALGOS:
             return self._fail(f"wino6_gemm: algo={d.algo}")
+        if self._r6(d.r) not in self._W6:
+            return self._fail("wino6_gemm: variant")
+        if not (d.U or d.U3) or not d.V or not d.M:
+            return self._fail("wino6_gemm: null pointer")
         T = self.nirgan_wino6_tiles_r(d.B, d.H, d.W, d.r)
         nplanes = self._geo6(self._r6(d.r))[2] ** 2
         if d.K <= 64 or d.K % 4 or d.C % 4 or d.V_elems < nplanes * T * d.C or d.M_elems < nplanes * T * d.K:
@@ -669,8 +678,18 @@ class EmuBackend:
             return self._fail(f"wino6_output: algo={d.algo}")
         B, H, W, K = d.B, d.H, d.W, d.K
         v = self._r6(d.r)
+        if v not in self._W6:
+            return self._fail("wino6_output: variant")
         r, mo, n = self._geo6(v)
         TH, TW = -(-H // mo), -(-W // mo)
+        if K % 4 or min(B, H - 1, W - 1, K) <= 0 or not d.M or not (d.y or d.fuse_gz):
+            return self._fail("wino6_output: bad shape / null pointer")
+        if d.M_elems < n * n * B * TH * TW * K:
+            return self._fail("wino6_output: M workspace too small")
+        if d.stats_ws and d.stats_ws_elems < B * TH * TW * 4 * K:
+            return self._fail("wino6_output: stats_ws too small")
+        if d.fuse_gz and (d.stats_ws or not (d.fuse_y and d.fuse_mean and d.fuse_rstd and d.fuse_part) or d.fuse_act not in (0, 1, 2)):
+            return self._fail("wino6_output: fused instance-norm backward: no forward statistics; fuse_y / mean / rstd / part; fuse_act")
         M = arr(d.M, n * n * B * TH * TW * K).reshape(n, n, B, TH, TW, K).astype(np.float64)
         AT = self._W6[v][2]
         Y = np.einsum("pa,albyxk,ql->bypxqk", AT, M, AT).reshape(B, mo * TH, mo * TW, K)
@@ -740,7 +759,7 @@ class EmuBackend:
             return self._fail("wino6_dy: variant")
         r, mo, n = self._geo6(v)
         TH, TW = -(-H // mo), -(-W // mo)
-        if d.Yt_elems < n * n * B * TH * TW * K or d.dy_hp != H + 2 * d.dy_pad:
+        if d.Yt_elems < n * n * B * TH * TW * K or d.dy_hp != H + 2 * d.dy_pad or d.dy_wp != W + 2 * d.dy_pad or K % 4 or d.dy_pad < 0:
             return self._fail("wino6_dy: bad geometry / workspace")
         dy = arr(d.dy, B * d.dy_hp * d.dy_wp * K).reshape(B, d.dy_hp, d.dy_wp, K).astype(np.float64)
         z = np.zeros((B, mo * TH, mo * TW, K))
@@ -755,8 +774,11 @@ class EmuBackend:
         c, y = obj(cref), obj(yref)
         v = self._r6(c.r)
         r = self._geo6(v)[0]
-        if c.x != y.dy or y.dy_pad != r - 1 or c.H != y.H + r - 1 or c.W != y.W + r - 1 or c.C != y.K or self._r6(y.r) != v:
+        if (c.x != y.dy or y.dy_pad != r - 1 or c.H != y.H + r - 1 or c.W != y.W + r - 1 or c.C != y.K or self._r6(y.r) != v or y.B != c.B
+                or y.dy_hp != c.x_hp or y.dy_wp != c.x_wp):
             return self._fail("wino6_input_dy: the two descriptors do not describe the same output-gradient buffer")
+        if v in self._W6 and y.Yt_elems < self._geo6(v)[2] ** 2 * self.nirgan_wino6_tiles_r(y.B, y.H, y.W, v) * y.K:
+            return self._fail("wino6_input_dy: Yt workspace too small")          # (before V is written: a refused call writes nothing)
         rc = self.nirgan_wino6_input(cref)
         return rc if rc else self.nirgan_wino6_dy(yref)
 
@@ -767,13 +789,19 @@ class EmuBackend:
         self.calls.append("wino6_dy_norm")
         if n.dy or not n.norm or n.B != c.B or n.C != c.C or n.H != y.H or n.W != y.W or self._r6(c.r) != 6 or c.C % 32:
             return self._fail("wino6_input_dy_norm: bad instance-norm descriptor")
-        full = type(n)()
-        C.memmove(C.byref(full), C.byref(n), C.sizeof(n))
-        full.dy, full.d_hp, full.d_wp, full.d_pad = y.dy, y.dy_hp, y.dy_wp, y.dy_pad
+        if c.B <= 0 or y.H <= 1 or y.W <= 1 or y.dy_pad != 2 or y.dy_hp != y.H + 4 or y.dy_wp != y.W + 4:
+            return self._fail("wino6_input_dy: the two descriptors do not describe the same output-gradient buffer")
+        # dY lives in a scratch buffer of the described geometry (zero halo 2): the buffer behind c->x / y->dy is neither read nor written
+        scratch = np.zeros(c.B * y.dy_hp * y.dy_wp * c.C, dtype=np.float32)
+        full, c2, y2 = type(n)(), type(c)(), type(y)()
+        for dst, src in ((full, n), (c2, c), (y2, y)):
+            C.memmove(C.byref(dst), C.byref(src), C.sizeof(src))
+        full.dy, full.d_hp, full.d_wp, full.d_pad = scratch.ctypes.data, y.dy_hp, y.dy_wp, y.dy_pad
+        c2.x = y2.dy = scratch.ctypes.data
         mark = len(self.calls)
         rc = self.nirgan_instnorm_bwd(full)
         del self.calls[mark:]                 # the device runs no second instance-norm call: keep the call log as the device's
-        return rc if rc else self.nirgan_wino6_input_dy(cref, yref)
+        return rc if rc else self.nirgan_wino6_input_dy(c2, y2)
 
     def nirgan_wino6_wgrad_finish(self, slabs, nsplit, K, Cc, grad, accumulate, stream=None):
         return self.nirgan_wino6_wgrad_finish_r(slabs, nsplit, K, Cc, 3, grad, accumulate)
