@@ -843,6 +843,15 @@ typedef struct {
 /* names of the kernels the two launchers above pick for a descriptor (what a profile of the launch shows) */
 const char* nirgan_wino6_gemm_kernel_name(const nirgan_wino6_desc* d);
 const char* nirgan_wino6_pair_kernel_name(const nirgan_wino6_desc* d, const nirgan_wgrad_desc* w);
+/* ... and of the kernel a transform stage picks, from the fields its routing reads alone (r, C or K, algo, fuse_gz): pointers, extents and
+ * workspace sizes are NOT validated.  "" for a NULL descriptor, an unknown variant, stage or algo, and a stage the variant does not have
+ * (the normalising input of F(4x4,4x4); the dY-norm input and the fused output outside F(6x6,3x3), the former also needs C % 32 == 0).
+ * nirgan_wino6_dy has one kernel per variant, wino6_dy_kernel<r>. */
+#define NIRGAN_W6_STAGE_INPUT 0            /* nirgan_wino6_input and nirgan_wino6_input_dy: the same kernel */
+#define NIRGAN_W6_STAGE_INPUT_NORM 1       /* nirgan_wino6_input_norm */
+#define NIRGAN_W6_STAGE_INPUT_DY_NORM 2    /* nirgan_wino6_input_dy_norm */
+#define NIRGAN_W6_STAGE_OUTPUT 3           /* nirgan_wino6_output: the fused mode where d->fuse_gz is set */
+const char* nirgan_wino6_transform_kernel_name(const nirgan_wino6_desc* d, int stage);
 
 int64_t nirgan_wino6_tiles(int B, int H, int W);                   /* T of the 4x4-output variants */
 int64_t nirgan_wino6_tiles_r(int B, int H, int W, int r);          /* T of variant r (0 / 3, 4, 6); 0 for an unknown variant */

@@ -1281,16 +1281,31 @@ static inline bool w6_algo_known(int a) {
     return a == 0 || a == NIRGAN_W6_ONE_TILE || a == NIRGAN_W6_DIRECT_TILE || a == NIRGAN_W6_X3_R4 || a == NIRGAN_W6_PATCH_PER_THREAD || a == NIRGAN_W6_PATCH_PER_LANES;
 }
 #define W6_ALGOS "0, NIRGAN_W6_ONE_TILE, _DIRECT_TILE, _X3_R4, _PATCH_PER_THREAD or _PATCH_PER_LANES"
-static inline int w6_filter(int v) { return v == 6 ? 3 : v; }            // filter size
-static inline int w6_mo(int v) { return v == 6 ? 6 : 4; }                // outputs per tile and dimension
-static inline int w6_np(int v) { const int n = w6_mo(v) + w6_filter(v) - 1; return n * n; }      // planes: 36 / 49 / 64
-static inline long long w6_tiles(int B, int H, int W, int v) { const int m = w6_mo(v); return (long long)B * ((H + m - 1) / m) * ((W + m - 1) / m); }
+static inline bool w6_act_known(int a) { return a == NIRGAN_ACT_NONE || a == NIRGAN_ACT_RELU || a == NIRGAN_ACT_LRELU; }
+// The tile geometry of variant code `r` over B images of H x W outputs, in one place.  v: variant; r: filter size; mo: outputs per tile
+// and dimension; np: planes (36 / 49 / 64); T = B TH TW tiles
+struct W6Geo { int v, r, mo, np, TH, TW; long long T; };
+static W6Geo w6_geo(int B, int H, int W, int r) {
+    const int v = w6_r(r), f = v == 6 ? 3 : v, mo = v == 6 ? 6 : 4, n = mo + f - 1, TH = (H + mo - 1) / mo, TW = (W + mo - 1) / mo;
+    return {v, f, mo, n * n, TH, TW, (long long)B * TH * TW};
+}
+static W6Geo w6_geo(const nirgan_wino6_desc* d) { return w6_geo(d->B, d->H, d->W, d->r); }
+static W6Geo w6_geo(const nirgan_wino_dy_desc* y) { return w6_geo(y->B, y->H, y->W, y->r); }
+// f(integral_constant<int, v>) of a known variant v, for the kernels all three variants have
+template <class F> static inline void w6_variant(int v, F&& f) {
+    if (v == 3) f(std::integral_constant<int, 3>{});
+    else if (v == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 6>{});
+}
+// grids of 256 threads: the per-thread forms take a tile x W6VW<V> channels per thread, the lane-spread forms a tile x 32 channels per wave
+template <int V> static inline dim3 w6_thread_grid(long long T, int channels) { return dim3(unsigned((T * (channels / W6VW<V>::value) + 255) / 256)); }
+static inline dim3 w6_lane_grid(long long T, int channels) { return dim3(unsigned((T * (channels / 32) + 3) / 4)); }
 
 }  // namespace
 
 extern "C" int64_t nirgan_wino6_tiles_r(int B, int H, int W, int r) {
     if (B <= 0 || H <= 0 || W <= 0 || !w6_known(w6_r(r))) return 0;
-    return w6_tiles(B, H, W, w6_r(r));
+    return w6_geo(B, H, W, r).T;
 }
 
 extern "C" int64_t nirgan_wino6_tiles(int B, int H, int W) { return nirgan_wino6_tiles_r(B, H, W, 3); }
@@ -1326,24 +1341,46 @@ extern "C" int nirgan_wino6_weights_batch(const int64_t* jobs_device, int njobs,
     return nirgan_check_launch("wino6_weights_batch");
 }
 
+// Which kernel an input transform runs on (one place: the launcher and nirgan_wino6_transform_kernel_name read it).  stage: the entry
+// form, NIRGAN_W6_STAGE_INPUT*.  W6I_NONE: an unknown variant or algo, or a form the variant does not have (the fused forms exist for
+// the 3x3 filter, the dY-norm form for F(6x6,3x3) with C % 32 == 0).
+enum W6InRoute { W6I_NONE, W6I_THREAD3, W6I_THREAD4, W6I_THREAD6, W6I_THREAD3_NORM, W6I_THREAD6_NORM, W6I_LANES4, W6I_LANES6, W6I_LANES6_NORM, W6I_LANES6_DY_NORM };
+static const char* const W6_IN_NAMES[] = {"", "wino6_input_kernel<3,0>", "wino6_input_kernel<4,0>", "wino6_input_kernel<6,0>", "wino6_input_kernel<3,1>", "wino6_input_kernel<6,1>",
+                                          "wino6_input_coop_kernel<4,0>", "wino6_input_coop_kernel<6,0>", "wino6_input_coop_kernel<6,1>", "wino6_input_coop_kernel<6,2>"};      // by W6InRoute
+static W6InRoute w6_input_route(const nirgan_wino6_desc* d, const int stage) {
+    const int v = w6_r(d->r);
+    const bool norm = stage == NIRGAN_W6_STAGE_INPUT_NORM;
+    if (!w6_known(v) || !w6_algo_known(d->algo) || (v == 4 && stage != NIRGAN_W6_STAGE_INPUT)) return W6I_NONE;
+    if (stage == NIRGAN_W6_STAGE_INPUT_DY_NORM) return v == 6 && d->C % 32 == 0 ? W6I_LANES6_DY_NORM : W6I_NONE;
+    // F(6x6,3x3) / F(4x4,4x4): the 8 x 8 / 7 x 7 patches spread over the lanes, one wave per (patch, 32 channels).  Measured inside the
+    // step (bs 16): dY pass 73.8 -> 61.5 us, plain input 43.6 -> 41.3 us; the normalising variant 41.7 -> 44.5 us, so that one keeps the
+    // patch-per-thread kernel unless asked (algo = NIRGAN_W6_PATCH_PER_LANES).  Alone, back to back, both forms move 5.3 TB/s.
+    if (v != 3 && d->C % 32 == 0 && d->algo != NIRGAN_W6_PATCH_PER_THREAD && (!norm || d->algo == NIRGAN_W6_PATCH_PER_LANES))
+        return norm ? W6I_LANES6_NORM : v == 6 ? W6I_LANES6 : W6I_LANES4;
+    if (norm) return v == 3 ? W6I_THREAD3_NORM : W6I_THREAD6_NORM;
+    return v == 3 ? W6I_THREAD3 : v == 4 ? W6I_THREAD4 : W6I_THREAD6;
+}
+
 static int w6_input_impl(const nirgan_wino6_desc* d, const nirgan_wino_dy_desc* y, const float* ny, const float* mean, const float* rstd,
                          int act, float slope, void* stream, const nirgan_in_bwd_desc* nb = nullptr) {
     NG_REQUIRE(d && d->V && (d->x || ny || nb), "wino6_input: null pointer");
-    const int v = w6_r(d->r), np = w6_np(v), r = w6_filter(v), mo = w6_mo(v);
+    const W6Geo g = w6_geo(d);
+    const int v = g.v, r = g.r, stage = nb ? NIRGAN_W6_STAGE_INPUT_DY_NORM : ny ? NIRGAN_W6_STAGE_INPUT_NORM : NIRGAN_W6_STAGE_INPUT;
     NG_REQUIRE(w6_known(v), "wino6_input: variant %d (3, 4 or 6)", v);
     NG_REQUIRE(w6_algo_known(d->algo), "wino6_input: algo=%d (" W6_ALGOS ")", d->algo);
-    NG_REQUIRE(r == 3 || (!ny && !nb), "wino6_input: the fused variants exist for the 3x3 filter");
-    NG_REQUIRE(!nb || (v == 6 && d->C % 32 == 0), "wino6_input_dy_norm: F(6x6,3x3) with C %% 32 == 0 only");
+    const W6InRoute route = w6_input_route(d, stage);
+    NG_REQUIRE(r == 3 || stage == NIRGAN_W6_STAGE_INPUT, "wino6_input: the fused variants exist for the 3x3 filter");
+    NG_REQUIRE(route != W6I_NONE, "wino6_input_dy_norm: F(6x6,3x3) with C %% 32 == 0 only");       // (what is left of W6I_NONE after the checks above)
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->C > 0 && d->C % 4 == 0, "wino6_input: bad shape B=%d H=%d W=%d C=%d", d->B, d->H, d->W, d->C);
     NG_REQUIRE(ny || (d->x_hp == d->H + r - 1 && d->x_wp == d->W + r - 1), "wino6_input: the input must be (H+%d) x (W+%d) (%dx%d for %dx%d)", r - 1, r - 1, d->x_hp, d->x_wp, d->H, d->W);
     NG_REQUIRE(ng_aligned16(d->x) && ng_aligned16(d->V) && ng_aligned16(ny) && ng_aligned16(mean) && ng_aligned16(rstd), "wino6_input: pointers must be 16-byte aligned");
-    const long long T = w6_tiles(d->B, d->H, d->W, v);
+    const long long T = g.T;
     NG_REQUIRE(T < (1ll << 31) / d->C, "wino6_input: problem too large for 32-bit tile offsets");
-    NG_REQUIRE(d->V_elems >= np * T * d->C, "wino6_input: V workspace too small");
+    NG_REQUIRE(d->V_elems >= g.np * T * d->C, "wino6_input: V workspace too small");
     W6In in;
     in.x = d->x; in.V = d->V; in.B = d->B; in.C = d->C;
     in.x_hp = d->H + r - 1; in.x_wp = d->W + r - 1; in.x_row = in.x_wp * d->C; in.x_img = in.x_hp * in.x_row;
-    in.TH = (d->H + mo - 1) / mo; in.TW = (d->W + mo - 1) / mo; in.T = T;
+    in.TH = g.TH; in.TW = g.TW; in.T = T;
     in.Yt = nullptr; in.yTH = in.yTW = 0; in.yT = 0;
     in.y = ny; in.mean = mean; in.rstd = rstd; in.H = d->H; in.W = d->W; in.act = act; in.slope = slope;
     if (y != nullptr) {
@@ -1352,16 +1389,11 @@ static int w6_input_impl(const nirgan_wino6_desc* d, const nirgan_wino_dy_desc* 
                    && y->dy_wp == d->x_wp && d->H == y->H + r - 1 && d->W == y->W + r - 1,
                    "wino6_input_dy: the two descriptors do not describe the same output-gradient buffer");
         NG_REQUIRE(ng_aligned16(y->Yt), "wino6_input_dy: pointers must be 16-byte aligned");
-        in.yTH = (y->H + mo - 1) / mo; in.yTW = (y->W + mo - 1) / mo; in.yT = (long long)y->B * in.yTH * in.yTW;
-        NG_REQUIRE(y->Yt_elems >= np * in.yT * y->K, "wino6_input_dy: Yt workspace too small");
+        const W6Geo yg = w6_geo(y);
+        in.yTH = yg.TH; in.yTW = yg.TW; in.yT = yg.T;
+        NG_REQUIRE(y->Yt_elems >= g.np * in.yT * y->K, "wino6_input_dy: Yt workspace too small");
         in.Yt = y->Yt;
     }
-    const long long nthreads = T * (d->C / (v == 3 ? 4 : 2));
-    const dim3 grid(unsigned((nthreads + 255) / 256));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // F(6x6,3x3): the 8 x 8 patches spread over the lanes, one wave per (patch, 32 channels).  Measured inside the step (bs 16):
-    // dY pass 73.8 -> 61.5 us, plain input 43.6 -> 41.3 us; the normalising variant 41.7 -> 44.5 us, so that one keeps the
-    // patch-per-thread kernel unless asked (algo = NIRGAN_W6_PATCH_PER_LANES).  Alone, back to back, both forms move 5.3 TB/s.
     in.nbB = 0;
     if (nb != nullptr) {
         NG_REQUIRE(y != nullptr && nb->norm && nb->y && nb->mean && nb->rstd && nb->ws && (nb->g || nb->g2 || nb->gsum_out), "wino6_input_dy_norm: the instance-norm descriptor needs y, mean, rstd, ws and a gradient");
@@ -1370,24 +1402,22 @@ static int w6_input_impl(const nirgan_wino6_desc* d, const nirgan_wino_dy_desc* 
         in.nb = in_bwd_params(nb);
         in.nbB = nb->B;
         NG_REQUIRE(nb->ws_elems >= int64_t(nb->B) * in.nb.pchunks * 2 * nb->C + int64_t(nb->B) * 2 * nb->C, "wino6_input_dy_norm: ws too small");
-        const dim3 cgrid(unsigned((T * (d->C / 32) + 3) / 4));
-        hipLaunchKernelGGL((wino6_input_coop_kernel<6, 2>), cgrid, dim3(256), 0, st, in);
-        return nirgan_check_launch("wino6_input_dy_norm");
     }
-    const bool coop = (v == 6 || v == 4) && d->C % 32 == 0 && d->algo != NIRGAN_W6_PATCH_PER_THREAD && (!ny || d->algo == NIRGAN_W6_PATCH_PER_LANES);
-    if (coop) {
-        const dim3 cgrid(unsigned((T * (d->C / 32) + 3) / 4));
-        if (ny) hipLaunchKernelGGL((wino6_input_coop_kernel<6, 1>), cgrid, dim3(256), 0, st, in);
-        else if (v == 6) hipLaunchKernelGGL((wino6_input_coop_kernel<6, 0>), cgrid, dim3(256), 0, st, in);
-        else hipLaunchKernelGGL((wino6_input_coop_kernel<4, 0>), cgrid, dim3(256), 0, st, in);
-        return nirgan_check_launch("wino6_input");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 lanes = w6_lane_grid(T, d->C);
+    switch (route) {
+    case W6I_NONE: return NIRGAN_ERR_ARG;       // (refused above, with its message)
+    case W6I_LANES6_DY_NORM: hipLaunchKernelGGL((wino6_input_coop_kernel<6, 2>), lanes, dim3(256), 0, st, in); break;
+    case W6I_LANES6_NORM: hipLaunchKernelGGL((wino6_input_coop_kernel<6, 1>), lanes, dim3(256), 0, st, in); break;
+    case W6I_LANES6: hipLaunchKernelGGL((wino6_input_coop_kernel<6, 0>), lanes, dim3(256), 0, st, in); break;
+    case W6I_LANES4: hipLaunchKernelGGL((wino6_input_coop_kernel<4, 0>), lanes, dim3(256), 0, st, in); break;
+    case W6I_THREAD3_NORM: hipLaunchKernelGGL((wino6_input_kernel<3, 1>), w6_thread_grid<3>(T, d->C), dim3(256), 0, st, in); break;
+    case W6I_THREAD6_NORM: hipLaunchKernelGGL((wino6_input_kernel<6, 1>), w6_thread_grid<6>(T, d->C), dim3(256), 0, st, in); break;
+    case W6I_THREAD3: case W6I_THREAD4: case W6I_THREAD6:
+        w6_variant(v, [&](auto V) { hipLaunchKernelGGL((wino6_input_kernel<decltype(V)::value, 0>), w6_thread_grid<decltype(V)::value>(T, d->C), dim3(256), 0, st, in); });
+        break;
     }
-    if (ny && v == 3) hipLaunchKernelGGL((wino6_input_kernel<3, 1>), grid, dim3(256), 0, st, in);
-    else if (ny) hipLaunchKernelGGL((wino6_input_kernel<6, 1>), grid, dim3(256), 0, st, in);
-    else if (v == 3) hipLaunchKernelGGL((wino6_input_kernel<3, 0>), grid, dim3(256), 0, st, in);
-    else if (v == 4) hipLaunchKernelGGL((wino6_input_kernel<4, 0>), grid, dim3(256), 0, st, in);
-    else hipLaunchKernelGGL((wino6_input_kernel<6, 0>), grid, dim3(256), 0, st, in);
-    return nirgan_check_launch("wino6_input");
+    return nirgan_check_launch(nb ? "wino6_input_dy_norm" : "wino6_input");
 }
 
 extern "C" int nirgan_wino6_input(const nirgan_wino6_desc* d, void* stream) { return w6_input_impl(d, nullptr, nullptr, nullptr, nullptr, 0, 0.f, stream); }
@@ -1399,7 +1429,7 @@ extern "C" int nirgan_wino6_input_dy(const nirgan_wino6_desc* d, const nirgan_wi
 
 extern "C" int nirgan_wino6_input_norm(const nirgan_wino6_desc* d, const float* y, const float* mean, const float* rstd, int act, float slope, void* stream) {
     NG_REQUIRE(y && mean && rstd, "wino6_input_norm: null pointer");
-    NG_REQUIRE(act == NIRGAN_ACT_NONE || act == NIRGAN_ACT_RELU || act == NIRGAN_ACT_LRELU, "wino6_input_norm: activation %d", act);
+    NG_REQUIRE(w6_act_known(act), "wino6_input_norm: activation %d", act);
     return w6_input_impl(d, nullptr, y, mean, rstd, act, slope, stream);
 }
 
@@ -1410,34 +1440,32 @@ extern "C" int nirgan_wino6_input_dy_norm(const nirgan_wino6_desc* d, const nirg
 
 extern "C" int nirgan_wino6_dy(const nirgan_wino_dy_desc* d, void* stream) {
     NG_REQUIRE(d && d->dy && d->Yt, "wino6_dy: null pointer");
-    const int v = w6_r(d->r), mo = w6_mo(v);
-    NG_REQUIRE(w6_known(v), "wino6_dy: variant %d (3, 4 or 6)", v);
+    const W6Geo g = w6_geo(d);
+    NG_REQUIRE(w6_known(g.v), "wino6_dy: variant %d (3, 4 or 6)", g.v);
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->K > 0 && d->K % 4 == 0 && d->dy_pad >= 0, "wino6_dy: bad shape");
     NG_REQUIRE(d->dy_hp == d->H + 2 * d->dy_pad && d->dy_wp == d->W + 2 * d->dy_pad, "wino6_dy: dy geometry mismatch");
     NG_REQUIRE(ng_aligned16(d->dy) && ng_aligned16(d->Yt), "wino6_dy: pointers must be 16-byte aligned");
     W6Dy p;
     p.dy = d->dy; p.Yt = d->Yt; p.B = d->B; p.H = d->H; p.W = d->W; p.K = d->K;
     p.d_row = d->dy_wp * d->K; p.d_img = d->dy_hp * p.d_row; p.d_org = d->dy_pad * p.d_row + d->dy_pad * d->K;
-    p.TH = (d->H + mo - 1) / mo; p.TW = (d->W + mo - 1) / mo; p.T = (long long)d->B * p.TH * p.TW;
-    NG_REQUIRE(d->Yt_elems >= w6_np(v) * p.T * d->K, "wino6_dy: workspace too small");
-    const long long n = p.T * (d->K / (v == 3 ? 4 : 2));
-    const dim3 grid(unsigned((n + 255) / 256));
-    if (v == 3) hipLaunchKernelGGL(wino6_dy_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else if (v == 4) hipLaunchKernelGGL(wino6_dy_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else hipLaunchKernelGGL(wino6_dy_kernel<6>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    p.TH = g.TH; p.TW = g.TW; p.T = g.T;
+    NG_REQUIRE(d->Yt_elems >= g.np * p.T * d->K, "wino6_dy: workspace too small");
+    w6_variant(g.v, [&](auto V) {
+        hipLaunchKernelGGL(wino6_dy_kernel<decltype(V)::value>, w6_thread_grid<decltype(V)::value>(p.T, d->K), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    });
     return nirgan_check_launch("wino6_dy");
 }
 
 // validation + the 32-k form's parameters (one plane as a 1x1 'convolution' over a [1][T] image of C-channel pixels: the direct tile's descriptor)
 static int w6_gemm_params(const nirgan_wino6_desc* d, W6Gemm& g, long long& T) {
     NG_REQUIRE(d && (d->U || d->U3) && d->V && d->M && d->zero_page, "wino6_gemm: null pointer");
-    const int v = w6_r(d->r), np = w6_np(v);
-    NG_REQUIRE(w6_known(v), "wino6_gemm: variant %d (3, 4 or 6)", v);
+    const W6Geo geo = w6_geo(d);
+    NG_REQUIRE(w6_known(geo.v), "wino6_gemm: variant %d (3, 4 or 6)", geo.v);
     NG_REQUIRE(w6_algo_known(d->algo), "wino6_gemm: algo=%d (" W6_ALGOS ")", d->algo);
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->C > 0 && d->C % 4 == 0 && d->K > 64 && d->K % 4 == 0, "wino6_gemm: C %% 4 == 0, K > 64, K %% 4 == 0 (C=%d K=%d)", d->C, d->K);
-    T = w6_tiles(d->B, d->H, d->W, v);
+    T = geo.T;
     NG_REQUIRE(T * d->C < (1ll << 31) && T * d->K < (1ll << 31), "wino6_gemm: problem too large for 32-bit offsets");
-    NG_REQUIRE(d->V_elems >= np * T * d->C && d->M_elems >= np * T * d->K, "wino6_gemm: V / M workspace too small");
+    NG_REQUIRE(d->V_elems >= geo.np * T * d->C && d->M_elems >= geo.np * T * d->K, "wino6_gemm: V / M workspace too small");
     nirgan_conv_desc c = {};
     c.in = d->V; c.in_elems = T * d->C; c.in_hp = 1; c.in_wp = int(T); c.in_cs = d->C; c.run = d->C; c.in_stride = 1;
     c.ntaps = 1;
@@ -1449,7 +1477,7 @@ static int w6_gemm_params(const nirgan_wino6_desc* d, W6Gemm& g, long long& T) {
     const int rc = ng::build_conv_params(&c, g.p);
     if (rc != NIRGAN_OK) return rc;
     g.in_plane = T * d->C; g.w_plane = (long long)d->K * d->C; g.out_plane = T * d->K;
-    g.per_plane = g.p.mtiles * g.p.ntiles; g.total = np * g.per_plane;
+    g.per_plane = g.p.mtiles * g.p.ntiles; g.total = geo.np * g.per_plane;
     return NIRGAN_OK;
 }
 
@@ -1460,7 +1488,7 @@ static int w6_gemm_params(const nirgan_wino6_desc* d, W6Gemm& g, long long& T) {
 // (the persistent bodies address a plane with 32-bit BYTE offsets, unsigned(row * C + chunk) * 4: T * C and K * C must stay below 2^30;
 // larger problems take the one-tile-per-workgroup kernels)
 static bool w6_persistent_ok(const nirgan_wino6_desc* d, bool pair = true) {
-    const long long T = w6_tiles(d->B, d->H, d->W, w6_r(d->r));
+    const long long T = w6_geo(d).T;
     if (T * d->C >= (1ll << 30) || (long long)d->K * d->C >= (1ll << 30) || T * d->K >= (1ll << 30)) return false;
     return d->C == 256 || (d->C == 512 && !pair);
 }
@@ -1468,7 +1496,7 @@ static bool w6_persistent_ok(const nirgan_wino6_desc* d, bool pair = true) {
 static W6G16 w6_g16_params(const nirgan_wino6_desc* d, long long T) {
     W6G16 q;
     q.A = d->V; q.Bw = d->U; q.Out = d->M; q.zero = d->zero_page; q.T = int(T); q.C = d->C; q.K = d->K;
-    q.mtiles = int((T + 127) / 128); q.ntiles = (d->K + 127) / 128; q.per_plane = q.mtiles * q.ntiles; q.total = w6_np(w6_r(d->r)) * q.per_plane;
+    q.mtiles = int((T + 127) / 128); q.ntiles = (d->K + 127) / 128; q.per_plane = q.mtiles * q.ntiles; q.total = w6_geo(d).np * q.per_plane;
     q.a_plane = T * d->C; q.b_plane = (long long)d->K * d->C; q.o_plane = T * d->K;
     return q;
 }
@@ -1476,10 +1504,11 @@ static W6G16 w6_g16_params(const nirgan_wino6_desc* d, long long T) {
 // precision 3 for the plane GEMMs: the three bf16 planes of U are there and the split tile's shapes apply; g.p then describes the
 // split tile's launch (nirgan_wino6_desc.algo = NIRGAN_W6_X3_R4 asks for the four-wave register-fed tile where it applies)
 static bool w6_x3(const nirgan_wino6_desc* d, W6Gemm& g) {
-    if (!(d->U3 != nullptr && d->C % 32 == 0 && d->K % 64 == 0 && g.p.off32 && (long long)w6_np(w6_r(d->r)) * d->K * d->C * 2 < (1ll << 40))) return false;
+    const long long planes = w6_geo(d).np;
+    if (!(d->U3 != nullptr && d->C % 32 == 0 && d->K % 64 == 0 && g.p.off32 && planes * d->K * d->C * 2 < (1ll << 40))) return false;
     g.p.prec = 3;
     g.p.w3 = static_cast<const unsigned short*>(d->U3);
-    g.p.w3_plane = (long long)w6_np(w6_r(d->r)) * d->K * d->C;
+    g.p.w3_plane = planes * d->K * d->C;
     g.p.algo = d->algo == NIRGAN_W6_X3_R4 ? NIRGAN_CONV_X3_R4 : 0;
     return true;
 }
@@ -1566,7 +1595,7 @@ extern "C" int nirgan_wino6_gemm(const nirgan_wino6_desc* d, void* stream) {
     const W6Route r = w6_gemm_route(d, g, false);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (r.k == W6_SPLIT3)        // precision 3: the plane GEMMs on the bf16 pipe, V split in the kernel, U from its three bf16 planes (nirgan_wino6_weights_x3)
-        return ng::ng_launch_conv_x3(&g.p, 1, r.bn, w6_np(w6_r(d->r)), g.in_plane, g.w_plane, g.out_plane, st, "wino6_gemm (three-term split tile)");
+        return ng::ng_launch_conv_x3(&g.p, 1, r.bn, w6_geo(d).np, g.in_plane, g.w_plane, g.out_plane, st, "wino6_gemm (three-term split tile)");
     NG_REQUIRE(d->U != nullptr, "wino6_gemm: U is required unless the three-term split tile takes the launch (U3, C %% 32 == 0, K %% 64 == 0)");
     if (r.k == W6_DIRECT) {
         hipLaunchKernelGGL(wino6_gemm_kernel, dim3(g.total), dim3(256), 0, st, g);
@@ -1581,45 +1610,61 @@ extern "C" int nirgan_wino6_gemm(const nirgan_wino6_desc* d, void* stream) {
     return nirgan_check_launch("wino6_gemm");
 }
 
+// Which kernel an output transform runs on (the launcher and nirgan_wino6_transform_kernel_name read it); the fused mode (fuse_gz) exists
+// for F(6x6,3x3).  W6O_NONE: an unknown variant or algo, or the fused mode of another variant.
+enum W6OutRoute { W6O_NONE, W6O_THREAD3, W6O_THREAD4, W6O_THREAD6, W6O_FUSED_THREAD6, W6O_FUSED_LANES6 };
+static const char* const W6_OUT_NAMES[] = {"", "wino6_output_kernel<3>", "wino6_output_kernel<4>", "wino6_output_kernel<6>", "wino6_output_inbwd_kernel<6>",
+                                           "wino6_output_inbwd_coop_kernel"};      // by W6OutRoute
+static W6OutRoute w6_output_route(const nirgan_wino6_desc* d) {
+    const int v = w6_r(d->r);
+    if (!w6_known(v) || !w6_algo_known(d->algo)) return W6O_NONE;
+    // (the plain output transform keeps the tile-per-thread kernel: its lane-spread form measured 39.8 against 35.3 us per launch)
+    if (d->fuse_gz == nullptr) return v == 3 ? W6O_THREAD3 : v == 4 ? W6O_THREAD4 : W6O_THREAD6;
+    if (v != 6) return W6O_NONE;
+    return d->K % 32 == 0 && d->algo != NIRGAN_W6_PATCH_PER_THREAD ? W6O_FUSED_LANES6 : W6O_FUSED_THREAD6;      // the tile spread over a wave's lanes
+}
+
+extern "C" const char* nirgan_wino6_transform_kernel_name(const nirgan_wino6_desc* d, int stage) {
+    if (!d || stage < NIRGAN_W6_STAGE_INPUT || stage > NIRGAN_W6_STAGE_OUTPUT) return "";
+    return stage == NIRGAN_W6_STAGE_OUTPUT ? W6_OUT_NAMES[w6_output_route(d)] : W6_IN_NAMES[w6_input_route(d, stage)];
+}
+
 extern "C" int nirgan_wino6_output(const nirgan_wino6_desc* d, void* stream) {
     NG_REQUIRE(d && d->M && (d->y || d->fuse_gz), "wino6_output: null pointer");
-    const int v = w6_r(d->r), mo = w6_mo(v);
+    const W6Geo g = w6_geo(d);
+    const int v = g.v, mo = g.mo;
     NG_REQUIRE(w6_known(v), "wino6_output: variant %d (3, 4 or 6)", v);
     NG_REQUIRE(w6_algo_known(d->algo), "wino6_output: algo=%d (" W6_ALGOS ")", d->algo);
     NG_REQUIRE(d->B > 0 && d->H > 1 && d->W > 1 && d->K > 0 && d->K % 4 == 0, "wino6_output: bad shape");
     NG_REQUIRE(ng_aligned16(d->M) && ng_aligned16(d->y) && ng_aligned16(d->bias), "wino6_output: pointers must be 16-byte aligned");
-    const long long T = w6_tiles(d->B, d->H, d->W, v);
-    NG_REQUIRE(d->M_elems >= w6_np(v) * T * d->K, "wino6_output: M workspace too small");
+    const long long T = g.T;
+    NG_REQUIRE(d->M_elems >= g.np * T * d->K, "wino6_output: M workspace too small");
     NG_REQUIRE(!d->stats_ws || (d->stats_ws_elems >= T * 4 * d->K && ng_aligned16(d->stats_ws)), "wino6_output: stats_ws too small (T * 4 * K floats) or unaligned");
+    const W6OutRoute route = w6_output_route(d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->fuse_gz != nullptr) {
         // the data gradient's output transform + the first pass of the consumer's instance-norm backward
-        NG_REQUIRE(v == 6 && !d->bias && !d->stats_ws, "wino6_output: the fused instance-norm backward pass is for F(6x6,3x3) data gradients (no bias, no forward statistics)");
+        NG_REQUIRE(route != W6O_NONE && !d->bias && !d->stats_ws, "wino6_output: the fused instance-norm backward pass is for F(6x6,3x3) data gradients (no bias, no forward statistics)");
         NG_REQUIRE(d->fuse_y && d->fuse_mean && d->fuse_rstd && d->fuse_part, "wino6_output: fuse_y / fuse_mean / fuse_rstd / fuse_part required with fuse_gz");
         NG_REQUIRE(ng_aligned16(d->fuse_y) && ng_aligned16(d->fuse_mean) && ng_aligned16(d->fuse_rstd) && ng_aligned16(d->fuse_g2) && ng_aligned16(d->fuse_gz) && ng_aligned16(d->fuse_part),
                    "wino6_output: fuse pointers must be 16-byte aligned");
         NG_REQUIRE(d->H >= 6 && d->W >= 6 && (d->H - 3) / mo == (d->H - 1) / mo && (d->W - 3) / mo == (d->W - 1) / mo,
                    "wino6_output: the far halo line and its fold partner must share a tile (H=%d W=%d tile %d)", d->H, d->W, mo);
         NG_REQUIRE(d->fuse_part_elems >= T * 2 * d->K, "wino6_output: fuse_part too small");
-        NG_REQUIRE(d->fuse_act == NIRGAN_ACT_NONE || d->fuse_act == NIRGAN_ACT_RELU || d->fuse_act == NIRGAN_ACT_LRELU, "wino6_output: fuse_act %d", d->fuse_act);
-        W6Out pf{d->M, nullptr, nullptr, d->B, d->H, d->W, d->K, (d->H + mo - 1) / mo, (d->W + mo - 1) / mo, T, nullptr};
-        const long long nf = T * (d->K / (v == 3 ? 4 : 2));
-        const dim3 gridf(unsigned((nf + 255) / 256));
-        hipStream_t sf = static_cast<hipStream_t>(stream);
-        if (d->K % 32 == 0 && d->algo != NIRGAN_W6_PATCH_PER_THREAD) {      // the tile spread over a wave's lanes
-            const dim3 cgrid(unsigned((T * (d->K / 32) + 3) / 4));
-            hipLaunchKernelGGL(wino6_output_inbwd_coop_kernel, cgrid, dim3(256), 0, sf, pf, d->fuse_y, d->fuse_mean, d->fuse_rstd, d->fuse_g2, d->fuse_gz, d->fuse_part, d->fuse_act, d->fuse_slope);
-            return nirgan_check_launch("wino6_output");
-        }
-        hipLaunchKernelGGL(wino6_output_inbwd_kernel<6>, gridf, dim3(256), 0, sf, pf, d->fuse_y, d->fuse_mean, d->fuse_rstd, d->fuse_g2, d->fuse_gz, d->fuse_part, d->fuse_act, d->fuse_slope);
-        return nirgan_check_launch("wino6_output");
+        NG_REQUIRE(w6_act_known(d->fuse_act), "wino6_output: fuse_act %d", d->fuse_act);
     }
-    W6Out p{d->M, d->bias, d->y, d->B, d->H, d->W, d->K, (d->H + mo - 1) / mo, (d->W + mo - 1) / mo, T, d->stats_ws};
-    // (the plain output transform keeps the tile-per-thread kernel: its lane-spread form measured 39.8 against 35.3 us per launch)
-    const long long n = T * (d->K / (v == 3 ? 4 : 2));
-    const dim3 grid(unsigned((n + 255) / 256));
-    if (v == 3) hipLaunchKernelGGL(wino6_output_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else if (v == 4) hipLaunchKernelGGL(wino6_output_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else hipLaunchKernelGGL(wino6_output_kernel<6>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    const W6Out p{d->M, d->bias, d->fuse_gz ? nullptr : d->y, d->B, d->H, d->W, d->K, g.TH, g.TW, T, d->stats_ws};     // (the fused mode: no bias, no statistics, y not written)
+    const auto fused = [&](auto kernel, const dim3 grid) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p, d->fuse_y, d->fuse_mean, d->fuse_rstd, d->fuse_g2, d->fuse_gz, d->fuse_part, d->fuse_act, d->fuse_slope);
+    };
+    switch (route) {
+    case W6O_NONE: return NIRGAN_ERR_ARG;       // (refused above, with its message)
+    case W6O_FUSED_LANES6: fused(wino6_output_inbwd_coop_kernel, w6_lane_grid(T, d->K)); break;
+    case W6O_FUSED_THREAD6: fused(wino6_output_inbwd_kernel<6>, w6_thread_grid<6>(T, d->K)); break;
+    case W6O_THREAD3: case W6O_THREAD4: case W6O_THREAD6:
+        w6_variant(v, [&](auto V) { hipLaunchKernelGGL(wino6_output_kernel<decltype(V)::value>, w6_thread_grid<decltype(V)::value>(T, d->K), dim3(256), 0, st, p); });
+        break;
+    }
     return nirgan_check_launch("wino6_output");
 }
 
@@ -1636,9 +1681,7 @@ extern "C" int nirgan_wino6_wgrad_finish_r(const float* slabs, int nsplit, int K
     W6Fin p{slabs, nsplit, K, C, grad, accumulate ? 1 : 0};
     const long long n = (long long)K * C;
     const dim3 grid(unsigned((n + 63) / 64));
-    if (r == 3) hipLaunchKernelGGL(wino6_wgrad_finish_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else if (r == 4) hipLaunchKernelGGL(wino6_wgrad_finish_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    else hipLaunchKernelGGL(wino6_wgrad_finish_kernel<6>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    w6_variant(r, [&](auto V) { hipLaunchKernelGGL(wino6_wgrad_finish_kernel<decltype(V)::value>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p); });
     return nirgan_check_launch("wino6_wgrad_finish");
 }
 
@@ -1656,9 +1699,7 @@ extern "C" int nirgan_wino6_wgrad_finish_batch(const float* const* slabs, float*
     const long long kc = (long long)K * C;
     const dim3 grid(unsigned((kc + 63) / 64), unsigned(n));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (r == 3) hipLaunchKernelGGL(wino6_wgrad_finish_batch_kernel<3>, grid, dim3(256), 0, st, b);
-    else if (r == 4) hipLaunchKernelGGL(wino6_wgrad_finish_batch_kernel<4>, grid, dim3(256), 0, st, b);
-    else hipLaunchKernelGGL(wino6_wgrad_finish_batch_kernel<6>, grid, dim3(256), 0, st, b);
+    w6_variant(r, [&](auto V) { hipLaunchKernelGGL(wino6_wgrad_finish_batch_kernel<decltype(V)::value>, grid, dim3(256), 0, st, b); });
     return nirgan_check_launch("wino6_wgrad_finish_batch");
 }
 

@@ -240,7 +240,8 @@ class Wino6Desc(C.Structure):
 
 W6_ONE_TILE, W6_DIRECT_TILE, W6_X3_R4 = 1, 3, 5                                  # nirgan_wino6_desc.algo
 W6_PATCH_PER_THREAD, W6_PATCH_PER_LANES = 16, 17                                 # nirgan_wino6_desc.algo for the input transforms (A/B)
-WGRAD_ONE_UNIT, WGRAD_TILE128 = 1, 2                      # nirgan_wgrad_desc.algo
+W6_STAGE_INPUT, W6_STAGE_INPUT_NORM, W6_STAGE_INPUT_DY_NORM, W6_STAGE_OUTPUT = 0, 1, 2, 3   # nirgan_wino6_transform_kernel_name's stage
+WGRAD_ONE_UNIT, WGRAD_TILE128 = 1, 2                     # nirgan_wgrad_desc.algo
 CONV_TILE128, CONV_X3_R4 = 1, 4                            # nirgan_conv_desc.algo
 
 
@@ -298,6 +299,7 @@ PROTOTYPES = {
     "nirgan_wino6_gemm_wgrad_pair": (i32, [C.POINTER(Wino6Desc), C.POINTER(WgradDesc), fp]),
     "nirgan_wino6_gemm_kernel_name": (C.c_char_p, [C.POINTER(Wino6Desc)]),
     "nirgan_wino6_pair_kernel_name": (C.c_char_p, [C.POINTER(Wino6Desc), C.POINTER(WgradDesc)]),
+    "nirgan_wino6_transform_kernel_name": (C.c_char_p, [C.POINTER(Wino6Desc), i32]),
     "nirgan_wino6_output": (i32, [C.POINTER(Wino6Desc), fp]),
     "nirgan_wino6_conv3x3": (i32, [C.POINTER(Wino6Desc), fp]),
     "nirgan_wino6_dy": (i32, [C.POINTER(WinoDyDesc), fp]),

@@ -665,6 +665,9 @@ class EmuBackend:
     def nirgan_wino6_pair_kernel_name(self, cref, wref):
         return b"emulated_wino6_pair"
 
+    def nirgan_wino6_transform_kernel_name(self, ref, stage):
+        return b"emulated_wino6_transform"
+
     def nirgan_wino6_gemm_wgrad_pair(self, cref, wref, stream=None):
         if obj(wref).algo not in WGRAD_ALGOS:
             return self._fail(f"wgrad_igemm: algo={obj(wref).algo}")

@@ -46,6 +46,27 @@ def test_the_case_tables_name_every_route_and_shape_reason():
     assert {c.kind for c in S.DYNORM_CASES} == {"fold", "skip", "pre"} and all(c.shape[3] % 32 == 0 for c in S.DYNORM_CASES)
 
 
+def test_the_library_routes_every_transform_case_to_the_kernel_its_table_names():
+    """the compiled library's own routing, asked without a launch (the query reads r, C / K, algo and fuse_gz alone, so it needs no GPU);
+    the bodies ask again on the device with the descriptor they launch"""
+    name = L.backend().nirgan_wino6_transform_kernel_name
+
+    def named(v, ch, algo, stage, fused=False):
+        d = L.Wino6Desc()
+        d.r, d.C, d.K, d.algo, d.fuse_gz = v, ch, ch, algo, (16 if fused else None)
+        return name(C.byref(d), stage).decode()
+
+    for c in S.IN_CASES:
+        if c.entry != "dy":
+            assert named(c.v, c.C, c.algo, S.IN_STAGE[c.entry]) == c.kernel, c
+    for c in S.DYNORM_CASES:
+        assert named(6, c.shape[3], 0, L.W6_STAGE_INPUT_DY_NORM) == S.DYNORM_KERNEL, c
+    for c in S.OUT_CASES:
+        assert named(c.v, c.K, 0, L.W6_STAGE_OUTPUT) == c.kernel, c
+    for c in S.FUSE_CASES:
+        assert named(6, c.K, c.algo, L.W6_STAGE_OUTPUT, fused=True) == c.kernel, c
+
+
 @pytest.mark.parametrize("case", S.IN_CASES, ids=ident)
 def test_input_transform(emu, case):
     S.input_against_float64("cpu", case)

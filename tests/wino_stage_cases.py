@@ -44,7 +44,9 @@ are declared to it (V_elems, M_elems, Yt_elems exceed the need), weight_path_cas
 every owned element was written, everything else still holds the sentinel, and a second launch gives the same bits.  In the fused mode y
 is passed and must stay untouched.
 
-Worst err / bound measured on the MI355X per family (RATIO lines; integer passes are bitwise and have no ratio):
+Worst err / bound measured on the MI355X per family (RATIO lines; integer passes are bitwise and have no ratio).  The kernel in a family's
+name is the one the launch ran on: every case asserts on the device that the library's routing (nirgan_wino6_transform_kernel_name,
+_gemm_kernel_name, _pair_kernel_name: the functions the launchers switch on) names its table's kernel; nirgan_wino6_dy has one per variant:
 
     in_bwd means (ws)                                                      0.409
     wino6_dy r3 Yt wino6_dy_kernel<3>                                      0.144
@@ -290,8 +292,8 @@ def f32_slope(s):
 
 # ---------------------------------------------------------------------------------------------------------------- stage 1: input transforms
 # entry: "input" | "input_norm" | "input_dy" | "dy".  hw: the layer's extent (for input_dy and dy: dY's extent).  opt: input_norm the
-# activation, dy the halo width dy_pad.  kernel: what the routing conditions of w6_input_impl / nirgan_wino6_dy give (in_route below
-# restates them; the table is asserted against it and must name every instantiation)
+# activation, dy the halo width dy_pad.  kernel: as nirgan_wino6_transform_kernel_name reports it (asserted on the device in every case;
+# nirgan_wino6_dy has one kernel per variant and no query); the table must name every instantiation
 In = namedtuple("In", "entry v C hw B algo opt kernel")
 PT, PL = L.W6_PATCH_PER_THREAD, L.W6_PATCH_PER_LANES
 IN_CASES = [
@@ -364,13 +366,14 @@ IN_KERNELS = {"wino6_input_kernel<3,0>", "wino6_input_kernel<4,0>", "wino6_input
               "wino6_dy_kernel<6>"}            # wino6_input_coop_kernel<6,2> is nirgan_wino6_input_dy_norm's: DYNORM_CASES
 
 
-def in_route(c):
-    """the routing conditions of csrc/wino6.hip::w6_input_impl / nirgan_wino6_dy, restated"""
-    if c.entry == "dy":
-        return f"wino6_dy_kernel<{c.v}>"
-    norm = c.entry == "input_norm"
-    coop = c.v in (6, 4) and c.C % 32 == 0 and c.algo != PT and (not norm or c.algo == PL)
-    return f"wino6_input_{'coop_' if coop else ''}kernel<{c.v},{int(norm)}>"
+IN_STAGE = {"input": L.W6_STAGE_INPUT, "input_dy": L.W6_STAGE_INPUT, "input_norm": L.W6_STAGE_INPUT_NORM}
+
+
+def ran_on(what, d, stage, kernel):
+    """the library's own routing decision for the launch of ``d`` names the table's kernel (the emulator has no kernels)"""
+    if not L.is_emulated():
+        name = L.backend().nirgan_wino6_transform_kernel_name(C.byref(d), stage).decode()
+        assert name == kernel, f"{what}: the launch takes {name!r}"
 
 
 def in_extent(c):
@@ -390,7 +393,7 @@ def in_blocks(c):
 def in_table_conditions_hold():
     assert {c.kernel for c in IN_CASES} == IN_KERNELS
     for c in IN_CASES:
-        assert in_route(c) == c.kernel, c
+        assert c.entry != "dy" or c.kernel == f"wino6_dy_kernel<{c.v}>", c        # one kernel per variant: nothing to route
         assert c.C % 4 == 0 and min(c.hw) > 1
     for fam in ("wino6_input_kernel", "wino6_input_coop_kernel", "wino6_dy_kernel"):           # the kernels that remap blockIdx
         counts = {in_blocks(c) for c in IN_CASES if c.kernel.startswith(fam + "<")}
@@ -514,6 +517,8 @@ def input_against_float64(dev, c):
             y = dy_desc(c, dyt.data_ptr(), c.opt, Yt, n_yt)
             launch = lambda: L.call("nirgan_wino6_dy", C.byref(y), st)
             src = dyt
+        if c.entry != "dy":
+            ran_on(what, d, IN_STAGE[c.entry], c.kernel)
         before = src.cpu().view(torch.int32).clone()
         twice(dev, launch, outs)
         assert torch.equal(src.cpu().view(torch.int32), before), f"{what}: the input buffer was written"
@@ -748,6 +753,7 @@ def output_against_float64(dev, c):
         d.M, d.M_elems, d.y, d.bias = Md.data_ptr(), Md.numel(), y.ptr, (bd.data_ptr() if c.bias else None)
         if c.stats:
             d.stats_ws, d.stats_ws_elems = stats.ptr, n_s + SLACK
+        ran_on(what, d, L.W6_STAGE_OUTPUT, c.kernel)
         before = Md.cpu().clone()
         twice(dev, lambda: L.call("nirgan_wino6_output", C.byref(d), st), [y, stats])
         assert torch.equal(Md.cpu(), before)
@@ -787,7 +793,6 @@ def fuse_table_conditions_hold():
         assert {c.hw for c in cs} >= {(6, 6), (6, 9), (9, 6), (10, 11), (12, 12), (11, 15)}
         assert {c.g2 for c in cs} == {True, False} and {c.act for c in cs} == {NONE, RELU, LRELU}
     for c in FUSE_CASES:
-        assert c.kernel == (COOPK if c.K % 32 == 0 and c.algo != PT else PAIRK)
         assert all((e - 3) // 6 == (e - 1) // 6 and e >= 6 for e in c.hw)
     assert {(e - 3) % 6 for c in FUSE_CASES for e in c.hw} >= {0, 1, 2, 3}           # the far fold's line at tile offsets 0 .. 3
     assert any(c.kernel == PAIRK and -(-c.B * int(np.prod(tiles_of(*c.hw, 6))) * (c.K // 2) // 256) > 1
@@ -868,6 +873,7 @@ def fused_output_run(dev, c, integer):
     d.M, d.M_elems, d.y = Md.data_ptr(), Md.numel(), y.ptr
     d.fuse_y, d.fuse_mean, d.fuse_rstd, d.fuse_g2 = yd.data_ptr(), md.data_ptr(), sd.data_ptr(), (g2.data_ptr() if c.g2 else None)
     d.fuse_gz, d.fuse_part, d.fuse_part_elems, d.fuse_act, d.fuse_slope = gz.ptr, part.ptr, n_p + SLACK, c.act, o["slope"]
+    ran_on(what, d, L.W6_STAGE_OUTPUT, c.kernel)
     twice(dev, lambda: L.call("nirgan_wino6_output", C.byref(d), st), [gz, part, y])
     untouched(what + " y", y)
     return owned(what + " fuse_gz", gz, n_g).reshape(o["ga"].shape), owned(what + " fuse_part", part, n_p).reshape(o["part"].shape)
@@ -886,8 +892,9 @@ def fused_output_against_float64(dev, c):
         what = f"{tuple(c)} {'integer' if integer else 'random'}"
         ga, part = fused_output_run(dev, c, integer)
         fused_checks(c, integer, ga, part)
-        if c.algo == PT and c.K % 32 == 0:          # the two forms: g_a bitwise equal, as the lane-spread kernel's comment promises
-            ga2, part2 = fused_output_run(dev, c._replace(algo=0, kernel=COOPK), integer)
+        twin = next(x for x in FUSE_CASES if x.algo == 0 and x[:3] + x[4:6] == c[:3] + c[4:6])       # the same shape on the default route
+        if c.algo == PT and twin.kernel == COOPK:   # the two forms: g_a bitwise equal, as the lane-spread kernel's comment promises
+            ga2, part2 = fused_output_run(dev, twin, integer)
             assert np.array_equal(ga.view(np.uint32), ga2.view(np.uint32)), f"{what}: g_a of the two forms differs"
 
 
@@ -910,6 +917,23 @@ def _base(dev, v, B, H, W, Cc, K, bufs):
     d.U, d.zero_page = bufs["x"].data_ptr(), bufs["zero"].data_ptr()
     d.V, d.V_elems, d.M, d.M_elems, d.y = bufs["V"].ptr, n * n * T * Cc, bufs["M"].ptr, n * n * T * K, bufs["y"].ptr
     return d, T
+
+
+def query_guards(be, D, stages, unsupported):
+    """nirgan_wino6_transform_kernel_name names no kernel for a NULL descriptor, an unknown variant, algo or stage, and for a stage the
+    variant does not have (``unsupported``: (descriptor, stage) pairs); the emulator has no kernels to name"""
+    if L.is_emulated():
+        return
+    name = be.nirgan_wino6_transform_kernel_name
+    for stage in stages:
+        assert name(C.byref(D()), stage), f"stage {stage}: a valid descriptor names no kernel"
+        assert name(None, stage) == b"", f"stage {stage}: NULL descriptor"
+        assert name(C.byref(D(r=5)), stage) == b"", f"stage {stage}: variant 5"
+        assert name(C.byref(D(algo=2)), stage) == b"", f"stage {stage}: retired algo 2"
+    for stage in (-1, 4):
+        assert name(C.byref(D()), stage) == b"", f"unknown stage {stage}"
+    for d, stage in unsupported:
+        assert name(C.byref(d), stage) == b"", f"stage {stage} of variant {d.r}, C = {d.C}"
 
 
 def input_guards(dev):
@@ -969,6 +993,8 @@ def input_guards(dev):
         y = Y(d)
         nb.B, nb.C, nb.H, nb.W = d.B, d.C, y.H, y.W
         R(f"input_dy_norm: {what}", be.nirgan_wino6_input_dy_norm(C.byref(d), C.byref(y), C.byref(nb), st))
+    query_guards(be, D, (L.W6_STAGE_INPUT, L.W6_STAGE_INPUT_NORM, L.W6_STAGE_INPUT_DY_NORM),
+                 [(D(v=4), L.W6_STAGE_INPUT_NORM), (D(v=4), L.W6_STAGE_INPUT_DY_NORM), (D(v=3), L.W6_STAGE_INPUT_DY_NORM), (D(Cc=36), L.W6_STAGE_INPUT_DY_NORM)])
 
 
 def gemm_guards(dev):
@@ -1030,6 +1056,7 @@ def output_guards(dev):
     R("output: fuse_part one element too small", be.nirgan_wino6_output(C.byref(D(fused=True, fuse_part_elems=2 * 2 * 2 * 2 * 32 - 1)), st))
     R("output: fused mode without fuse_y", be.nirgan_wino6_output(C.byref(D(fused=True, fuse_y=None)), st))
     R("output: fuse_act 3", be.nirgan_wino6_output(C.byref(D(fused=True, fuse_act=3)), st))
+    query_guards(be, D, (L.W6_STAGE_OUTPUT,), [(D(v=3, fused=True), L.W6_STAGE_OUTPUT), (D(v=4, fused=True), L.W6_STAGE_OUTPUT)])
 
 
 # ---------------------------------------------------------------------------------------------------------------- stage 1: the fused dY pass
@@ -1079,6 +1106,7 @@ def dynorm_against_float64(dev, c):
     case = In("input_dy", 6, Cc, (H, W), B, 0, 0, DYNORM_KERNEL)
     d = in_desc(case, Hd, Wd, hole.ptr, V, n_v)
     y = dy_desc(case, hole.ptr, 2, Yt, n_yt)
+    ran_on(what, d, L.W6_STAGE_INPUT_DY_NORM, DYNORM_KERNEL)
     ws_before = keep["ws"].cpu().clone()
     twice(dev, lambda: L.call("nirgan_wino6_input_dy_norm", C.byref(d), C.byref(y), C.byref(nd), st), [V, Yt])
     untouched(what + " the buffer behind c->x / y->dy", hole)
