@@ -1120,6 +1120,88 @@ typedef struct {
 } nirgan_raster_lookup_desc;
 int nirgan_raster_lookup(const nirgan_raster_lookup_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training batches from device-resident scenes (data/SR_dataset_RGB.py:24-56 of the reference: a rasterio stack, .astype(float32) /
+ * 10000, bands 0..2 = RGB, band 3 = NIR, coords = lon / lat of the centre pixel).  The training set stays in device memory as it is
+ * stored; a batch is cut, normalised, mirrored / rotated and georeferenced in one pass, and WHICH windows a batch holds is a pure
+ * function of (seed, draw, sample index): Philox4x32-10 as in the dropout section above, no generator state anywhere.
+ *
+ * The pool: ONE device buffer of uint16_t (NIRGAN_SCENE_U16) or float (NIRGAN_SCENE_F32) elements holding S scenes, scene s planar
+ * [C][H_s][W_s] from element table[s][0].  Nothing is aligned: offsets, widths and windows are arbitrary, every load is one element.
+ * table: int64 [S][NIRGAN_SCENE_TABLE_COLS] =
+ *     { element offset of the scene, H_s, W_s, cum_windows, element offset of the scene's invalid-prefix table in `prefix` or -1 }
+ * cum_windows[s] = sum over scenes 0 .. s of (H-T+1)*(W-T+1), a scene smaller than the tile T in either extent adding 0: the table
+ * belongs to one tile size.  table_host is the same table in HOST memory: every check reads it, device memory is not read for checks.
+ * geo: double [S][4] = (lon0, dlon, lat0, dlat), the outer corner of pixel [0][0] and the per-pixel steps of an axis-aligned
+ * EPSG:4326 grid; NULL = no coords are produced (coords is then not touched).
+ *
+ * nirgan_scene_invalid_prefix, for ONE scene: prefix [(H+1)][(W+1)] int32,
+ *     prefix[y][x] = number of invalid pixels (r, c) with r < y and c < x          (first row and first column 0)
+ * a pixel being invalid iff any of its four selected planes band[0..3] equals `nodata` (uint16 pool; compared as integers) or is NaN
+ * (float pool; nodata is ignored).  Integer arithmetic: exact, independent of any order.  Two launches, no atomics: a scan along
+ * every row (one wave per row, 64 pixels per step with a carry), then a running sum down every column in place.
+ * Argument errors (null pointer, unknown dtype, non-positive extent, (H+1)*(W+1) at 2^31 or more, a band outside 0 .. C-1, the scene
+ * outside the pool, nodata outside 0 .. 65535 for a uint16 pool) return NIRGAN_ERR_ARG before any launch.
+ *
+ * nirgan_scene_sample: TWO launches on the stream, no host synchronisation, no atomics.
+ *   Draw, one thread per sample b = 0 .. B-1.  Attempt a = 0 .. NIRGAN_SCENE_ATTEMPTS-1:
+ *     (w0, w1, w2, w3) = Philox4x32-10(key = (seed_lo, seed_hi), counter = (draw_lo, draw_hi, sample0 + b mod 2^32, a))
+ *     u    = w0 | w1 << 32;   idx = floor(u * total / 2^64)   with total = cum_windows[S-1]     (the high word of the 128-bit product)
+ *     s    = the first scene with cum_windows[s] > idx;   r = idx - cum_windows[s-1] (0 for s = 0);   nx = W_s - T + 1
+ *     y0   = r / nx;   x0 = r % nx;   view = w2 & (views - 1)
+ *     n    = P[y0+T][x0+T] - P[y0][x0+T] - P[y0+T][x0] + P[y0][x0]   with P the scene's prefix table; 0 where the scene has none
+ *            (table[s][4] < 0) or prefix is NULL
+ *   The first attempt with n <= max_invalid is taken; if none is, the LAST attempt is taken and `exhausted` is set.
+ *     window[b] = { s, y0, x0, view | a << 8 | exhausted << 31 }
+ *     coords[b] = { (float)(lon0 + ((x0 + T/2) + 0.5) * dlon), (float)(lat0 + ((y0 + T/2) + 0.5) * dlat) }
+ *   T/2 an integer division; the sum in the parentheses is exact; then ONE float64 product and ONE float64 sum, each rounded on its
+ *   own (no fused multiply-add), then one conversion to float: the centre of the centre pixel (SR_dataset_RGB.py:32).
+ *   Gather:  out[b][ch][i][j] = (float)src_s[band[ch]][y0 + i'][x0 + j'] / divisor      (one correctly rounded float32 division)
+ *   with (i', j') from (i, j) by the view rule of nirgan_tile_views_expand on the T x T window (bit 0 mirrors columns, bit 1 mirrors
+ *   rows, bit 2 transposes); ch 0..2 go to rgb [B][3][T][T], ch 3 to nir [B][1][T][T].  A float pool takes the same path with the
+ *   value as it is.  Every output element is written by one thread; the outputs need no initialisation.
+ * Argument errors return NIRGAN_ERR_ARG before any launch: a null pointer (d, pool, table, table_host, rgb, nir, window); unknown
+ * dtype; S or C non-positive, C < 4; views not 1, 4 or 8; a band outside 0 .. C-1; B, T or B*T*T non-positive or at 2^31 or more;
+ * divisor == 0 or NaN; max_invalid < 0; a table row with a negative offset, an extent outside 1 .. 2^31-1, a scene outside the pool,
+ * a cum_windows that is not the running sum for this T, a prefix offset without `prefix` or a prefix table outside prefix_elems; no
+ * scene holding a window (total == 0); total at 2^62 or more.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_SCENE_ATTEMPTS 8
+#define NIRGAN_SCENE_TABLE_COLS 5
+#define NIRGAN_SCENE_U16 0
+#define NIRGAN_SCENE_F32 1
+typedef struct {
+    const void* pool; int64_t pool_elems; /* the whole pool and its size in elements */
+    int dtype;                            /* NIRGAN_SCENE_U16 or NIRGAN_SCENE_F32 */
+    int64_t offset;                       /* element offset of the scene */
+    int C, H, W;
+    int band[4];
+    int nodata;                           /* uint16 pool: 0 .. 65535 */
+    int32_t* prefix;                      /* [(H+1)][(W+1)], OVERWRITTEN */
+} nirgan_scene_prefix_desc;
+typedef struct {
+    const void* pool; int64_t pool_elems;
+    int dtype;
+    int S, C;
+    const int64_t* table;                 /* device [S][NIRGAN_SCENE_TABLE_COLS] */
+    const int64_t* table_host;            /* the same table in HOST memory */
+    const int32_t* prefix; int64_t prefix_elems;   /* device: the scenes' invalid-prefix tables, or NULL */
+    const double* geo;                    /* device [S][4], or NULL */
+    int band[4];                          /* source planes of R, G, B, NIR */
+    int tile, B, views;                   /* views: 1, 4 or 8 */
+    float divisor;
+    uint32_t seed_lo, seed_hi;
+    uint64_t draw;
+    uint32_t sample0;                     /* index of this call's first sample in the logical batch (ranks, micro-batches) */
+    int max_invalid;
+    float* rgb;                           /* [B][3][T][T] */
+    float* nir;                           /* [B][1][T][T] */
+    float* coords;                        /* [B][2], or NULL */
+    int32_t* window;                      /* [B][4] */
+} nirgan_scene_sample_desc;
+int nirgan_scene_invalid_prefix(const nirgan_scene_prefix_desc* d, void* stream);
+int nirgan_scene_sample(const nirgan_scene_sample_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

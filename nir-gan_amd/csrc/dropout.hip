@@ -2,6 +2,7 @@
 // Philox4x32-10 per channel quad, keyed by the seed, counted by (quad index of the logical tensor, stream id, call): forward and
 // backward compute the same bits again, no mask tensor exists.  HBM-bound: ~60 integer operations per 32 bytes moved.
 #include "common.h"
+#include "philox_dev.h"
 
 namespace {
 
@@ -13,21 +14,6 @@ struct DropP {
     uint32_t stream_id;
     int sample0;
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 __global__ __launch_bounds__(256) void dropout_halo_kernel(const DropP p) {
     const uint32_t k0 = p.state[0], k1 = p.state[1], call = p.state[2];

@@ -179,6 +179,8 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
         kind.restore(ck)
         step, first_epoch = int(ck.get("global_step", 0)), int(ck.get("epoch", -1)) + 1
     for epoch in range(first_epoch, max_epochs):
+        if hasattr(train_loader, "set_epoch"):               # nirgan_hip.data.SceneLoader: a resumed run draws this epoch's batches
+            train_loader.set_epoch(epoch)
         model.train()
         for batch in train_loader:
             view = model.train_batch(_to_device(batch, device))

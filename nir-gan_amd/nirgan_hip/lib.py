@@ -226,6 +226,23 @@ class RasterLookupDesc(C.Structure):
                 ("has_nodata", i32), ("nodata", i32), ("value", fp)]
 
 
+SCENE_ATTEMPTS, SCENE_TABLE_COLS = 8, 5                   # include/nirgan_hip.h: NIRGAN_SCENE_ATTEMPTS / _TABLE_COLS
+SCENE_U16, SCENE_F32 = 0, 1                               # include/nirgan_hip.h: NIRGAN_SCENE_U16 / _F32
+SCENE_VIEWS = {"none": 1, "flips": 4, "d4": 8}            # include/nirgan_hip.h: nirgan_scene_sample_desc.views
+
+
+class ScenePrefixDesc(C.Structure):
+    _fields_ = [("pool", fp), ("pool_elems", i64), ("dtype", i32), ("offset", i64), ("C", i32), ("H", i32), ("W", i32),
+                ("band", i32 * 4), ("nodata", i32), ("prefix", fp)]
+
+
+class SceneSampleDesc(C.Structure):
+    _fields_ = [("pool", fp), ("pool_elems", i64), ("dtype", i32), ("S", i32), ("C", i32), ("table", fp), ("table_host", fp),
+                ("prefix", fp), ("prefix_elems", i64), ("geo", fp), ("band", i32 * 4), ("tile", i32), ("B", i32), ("views", i32),
+                ("divisor", f32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("draw", C.c_uint64), ("sample0", C.c_uint32),
+                ("max_invalid", i32), ("rgb", fp), ("nir", fp), ("coords", fp), ("window", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -286,6 +303,8 @@ PROTOTYPES = {
     "nirgan_region_boxes": (i32, [C.POINTER(PointRegionsDesc), fp]),
     "nirgan_point_regions": (i32, [C.POINTER(PointRegionsDesc), fp]),
     "nirgan_raster_lookup": (i32, [C.POINTER(RasterLookupDesc), fp]),
+    "nirgan_scene_invalid_prefix": (i32, [C.POINTER(ScenePrefixDesc), fp]),
+    "nirgan_scene_sample": (i32, [C.POINTER(SceneSampleDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
