@@ -1202,6 +1202,70 @@ typedef struct {
 int nirgan_scene_invalid_prefix(const nirgan_scene_prefix_desc* d, void* stream);
 int nirgan_scene_sample(const nirgan_scene_sample_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Multi-scale training batches from device-resident scenes (README.md:54 of the reference: "In order to make the model
+ * scale-agnostic, we randomly sample a derivative resolution from the datasets"; its datamodule is not part of the reference, so the
+ * behaviour is fixed HERE).  nirgan_scene_sample_scaled is nirgan_scene_sample with one more decision per sample: a resolution
+ * factor f out of K given ones.  The sample is a window of side L = f * T of the source, delivered as the T x T tile of the means of
+ * its f x f blocks -- the sensor's degradation for an integer factor, a box filter and nothing else.
+ *
+ * Pool, prefix, geo, band, views, divisor, seed, draw, sample0, rgb, nir, coords: as in nirgan_scene_sample_desc.
+ * factor[0 .. K-1]: strictly increasing, each in 1 .. NIRGAN_SCENE_MAX_FACTOR; weight[k] > 0 the integer weight of factor[k],
+ * Wtot = sum of the weights < 2^32; entries from K on are ignored.
+ * table / table_host: int64 [K][S][NIRGAN_SCENE_TABLE_COLS]; table k is EXACTLY the table nirgan_scene_sample wants for the tile side
+ * L_k = factor[k] * tile (same format; cum_windows the running sum for L_k), and is checked as that entry checks its own.
+ *
+ * TWO launches on the stream, no host synchronisation, no atomics.
+ *   Draw, one thread per sample b = 0 .. B-1.  With (v0, v1, v2, v3) = Philox4x32-10(key = (seed_lo, seed_hi), counter = (draw_lo,
+ *   draw_hi, sample0 + b mod 2^32, 0)), the call of attempt 0:
+ *     k    = the first k with weight[0] + .. + weight[k] > floor(v3 * Wtot / 2^32);   f = factor[k];   L = f * T
+ *   The scale is drawn ONCE per sample, from a word nirgan_scene_sample does not use: rejected attempts cannot move the mix of
+ *   scales towards those that reject less.  Then attempts a = 0 .. NIRGAN_SCENE_ATTEMPTS-1 run as in nirgan_scene_sample on table k
+ *   with T replaced by L (attempt 0 on the words above): u, idx with total = cum_windows_k[S-1], s, r, nx = W_s - L + 1, y0, x0,
+ *   view, and n the prefix-table count of the L x L window.  A window is accepted iff n <= (int64)max_invalid * f * f: max_invalid
+ *   counts invalid SOURCE pixels per output pixel's worth of area, the same invalid fraction at every scale.
+ *     window[b] = { s, y0, x0, view | a << 8 | (f - 1) << 16 | exhausted << 31 }          y0, x0 in SOURCE pixels
+ *     coords[b] = { (float)(lon0 + ((x0 + L/2) + 0.5) * dlon), (float)(lat0 + ((y0 + L/2) + 0.5) * dlat) }
+ *   L/2 an integer division, then ONE float64 product and ONE float64 sum, not fused, as there.
+ *   Gather:  D[ch][p][q] = the mean of src_s[band[ch]][y0 + p*f + rr][x0 + q*f + e], rr, e = 0 .. f-1:
+ *     uint16 pool:  S = the exact integer sum (at most 64 * 65535 < 2^24);   m = (float)S / (float)(f*f)     (one rounded division)
+ *     float pool:   S = a float64 sum, the f*f values added one after another in row-major order of the block (rr outer, e inner),
+ *                   starting from the first value;   m = (float)(S / (double)(f*f));   NaN propagates
+ *     out[b][ch][i][j] = D[ch][i'][j'] / divisor                                           (one correctly rounded float32 division)
+ *   with (i', j') from (i, j) by the view rule of nirgan_tile_views_expand on the T x T tile.  A nodata value inside an accepted
+ *   window is averaged like any other value: rejection bounds how many there are, nothing masks them.
+ *   For f = 1 every step is nirgan_scene_sample's arithmetic: with factor = {1} the window words, coords and pixels are bitwise its.
+ * Argument errors return NIRGAN_ERR_ARG before any launch: everything nirgan_scene_sample refuses, each table against its own L_k;
+ * K outside 1 .. NIRGAN_SCENE_MAX_SCALES; a factor outside 1 .. NIRGAN_SCENE_MAX_FACTOR or not above the one before it; a weight of
+ * 0; Wtot at 2^32 or more; L_k * L_k at 2^31 or more; a scale of which no scene holds a window (the message names the factor).
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_SCENE_MAX_SCALES 8
+#define NIRGAN_SCENE_MAX_FACTOR 8
+typedef struct {
+    const void* pool; int64_t pool_elems;
+    int dtype;
+    int S, C;
+    const int64_t* table;                 /* device [K][S][NIRGAN_SCENE_TABLE_COLS] */
+    const int64_t* table_host;            /* the same tables in HOST memory */
+    const int32_t* prefix; int64_t prefix_elems;
+    const double* geo;
+    int band[4];
+    int tile, B, views;                   /* tile: the side T of the DELIVERED tile */
+    float divisor;
+    uint32_t seed_lo, seed_hi;
+    uint64_t draw;
+    uint32_t sample0;
+    int max_invalid;                      /* invalid source pixels allowed per f x f block's worth of window area */
+    float* rgb;                           /* [B][3][T][T] */
+    float* nir;                           /* [B][1][T][T] */
+    float* coords;                        /* [B][2], or NULL */
+    int32_t* window;                      /* [B][4] */
+    int K;                                /* 1 .. NIRGAN_SCENE_MAX_SCALES */
+    int factor[8];
+    uint32_t weight[8];
+} nirgan_scene_scaled_desc;
+int nirgan_scene_sample_scaled(const nirgan_scene_scaled_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

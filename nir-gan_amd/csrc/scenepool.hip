@@ -13,14 +13,9 @@
 //           bytes per wave, so any T >= 1 needs no tail handling.
 // The prefix table of a scene is built once: a wave scans each row 64 pixels at a time with a carry, then one thread per column runs
 // the sum down in place (eight rows of loads in flight).  Integers throughout: exact and order-independent, no atomics.
-#include "common.h"
-#include "philox_dev.h"
+#include "scene_dev.h"
 
 namespace {
-
-constexpr int SP_B = 64;                 // side of the gather's block
-constexpr int SP_LD = SP_B + 1;          // padded LDS row
-constexpr int TC = NIRGAN_SCENE_TABLE_COLS;
 
 template <typename T> struct Elem;
 template <> struct Elem<uint16_t> {
@@ -105,14 +100,6 @@ struct SampleP {
     int32_t* window;
 };
 
-// a + x * y as one rounded float64 product and one rounded float64 sum.  __dmul_rn / __dadd_rn are plain operators in the compiler's
-// header and carry its default contraction with them when inlined, so the two operations stand here under the pragma instead.
-__device__ __forceinline__ double sp_mul_then_add(double a, double x, double y) {
-#pragma clang fp contract(off)
-    const double m = x * y;
-    return a + m;
-}
-
 __global__ __launch_bounds__(256) void scene_draw_kernel(const SampleP p) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
@@ -121,38 +108,14 @@ __global__ __launch_bounds__(256) void scene_draw_kernel(const SampleP p) {
     for (; a < NIRGAN_SCENE_ATTEMPTS; ++a) {
         uint32_t w[4];
         philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), uint32_t(a), p.seed_lo, p.seed_hi, w);
-        const uint64_t u = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
-        const int64_t idx = int64_t(__umul64hi(u, uint64_t(p.total)));          // < total
-        int lo = 0, hi = p.S - 1;                                              // the first scene with cum > idx (cum[S-1] = total > idx)
-        while (lo < hi) {
-            const int mid = lo + (hi - lo) / 2;
-            if (p.table[int64_t(mid) * TC + 3] > idx) hi = mid; else lo = mid + 1;
-        }
-        s = lo;
-        const int64_t* __restrict__ row = p.table + int64_t(s) * TC;
-        const int64_t r = idx - (s > 0 ? row[3 - TC] : 0);
-        const int64_t W = row[2], nx = W - p.T + 1;
-        y0 = int(r / nx);
-        x0 = int(r % nx);
-        view = int(w[2] & uint32_t(p.views - 1));
-        int64_t n = 0;
-        if (p.prefix && row[4] >= 0) {
-            const int32_t* __restrict__ P = p.prefix + row[4];
-            const int64_t ld = W + 1;
-            n = int64_t(P[(y0 + p.T) * ld + x0 + p.T]) - P[y0 * ld + x0 + p.T] - P[(y0 + p.T) * ld + x0] + P[y0 * ld + x0];
-        }
+        const int64_t n = sp_attempt(w, p.table, p.prefix, p.S, p.T, p.total, p.views, s, y0, x0, view);
         if (n <= p.max_invalid) { ok = true; break; }
     }
     if (!ok) a = NIRGAN_SCENE_ATTEMPTS - 1;
     int32_t* __restrict__ o = p.window + int64_t(b) * 4;
     o[0] = s; o[1] = y0; o[2] = x0;
     o[3] = int32_t(uint32_t(view) | (uint32_t(a) << 8) | (ok ? 0u : 0x80000000u));
-    if (p.geo && p.coords) {
-        const double* __restrict__ g = p.geo + int64_t(s) * 4;
-        const double cx = double(x0 + p.T / 2) + 0.5, cy = double(y0 + p.T / 2) + 0.5;      // exact
-        p.coords[int64_t(b) * 2 + 0] = float(sp_mul_then_add(g[0], cx, g[1]));
-        p.coords[int64_t(b) * 2 + 1] = float(sp_mul_then_add(g[2], cy, g[3]));
-    }
+    if (p.geo && p.coords) sp_centre(p.geo + int64_t(s) * 4, y0, x0, p.T, p.coords + int64_t(b) * 2);
 }
 
 template <typename T>
@@ -214,8 +177,6 @@ __global__ __launch_bounds__(256) void scene_gather_kernel(const SampleP p) {
     }
 }
 
-constexpr int64_t LIM31 = int64_t(1) << 31;
-
 }  // namespace
 
 extern "C" int nirgan_scene_invalid_prefix(const nirgan_scene_prefix_desc* d, void* stream) {
@@ -256,22 +217,9 @@ extern "C" int nirgan_scene_sample(const nirgan_scene_sample_desc* d, void* stre
     NG_REQUIRE(d->max_invalid >= 0, "scene_sample: negative max_invalid");
     NG_REQUIRE(d->pool_elems >= 0 && d->prefix_elems >= 0, "scene_sample: negative pool_elems or prefix_elems");
     int64_t total = 0;
-    for (int s = 0; s < d->S; ++s) {
-        const int64_t* r = d->table_host + int64_t(s) * TC;
-        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "scene_sample: scene %d has an extent outside 1 .. 2^31-1", s);
-        if (r[1] >= T && r[2] >= T) total += (r[1] - T + 1) * (r[2] - T + 1);   // each term below 2^62: the sum cannot wrap before the bound
-        NG_REQUIRE(total < (int64_t(1) << 62), "scene_sample: the pool has 2^62 windows or more");
-        NG_REQUIRE(r[3] == total, "scene_sample: cum_windows of scene %d is not the running window count for tile %d", s, d->tile);
-    }
+    if (int e = sp_check_table("scene_sample", d->table_host, d->S, T, &total)) return e;
     NG_REQUIRE(total > 0, "scene_sample: no scene holds a window of tile %d", d->tile);
-    for (int s = 0; s < d->S; ++s) {
-        const int64_t* r = d->table_host + int64_t(s) * TC;
-        NG_REQUIRE(r[0] >= 0 && r[0] <= d->pool_elems && r[1] * r[2] <= (d->pool_elems - r[0]) / d->C, "scene_sample: scene %d lies outside the pool", s);
-        if (r[4] >= 0) {
-            NG_REQUIRE(d->prefix, "scene_sample: scene %d names a prefix table but prefix is null", s);
-            NG_REQUIRE(r[4] <= d->prefix_elems && (r[1] + 1) * (r[2] + 1) <= d->prefix_elems - r[4], "scene_sample: the prefix table of scene %d lies outside prefix_elems", s);
-        }
-    }
+    if (int e = sp_check_extents("scene_sample", d->table_host, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
     SampleP p;
     p.pool = d->pool; p.table = d->table; p.prefix = d->prefix; p.geo = d->geo; p.total = total;
     for (int k = 0; k < 4; ++k) p.band[k] = d->band[k];

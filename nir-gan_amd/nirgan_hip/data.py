@@ -10,6 +10,11 @@ shared state -- rank r takes samples ``r * batch_size ..`` of the same logical b
     pool = ScenePool(scenes, nodata=0, geotransforms=geo)          # or ScenePool.from_npz(paths)
     fit(model, pool.loader(16, 256, steps_per_epoch=1000, seed=1), max_epochs=10)
 
+With ``scales`` every sample also draws a resolution factor f, cuts an f*T window and is delivered as the T x T tile of its f x f block
+means (``nirgan_scene_sample_scaled``): a 10 m pool then trains on 10, 20, 30 and 40 m tiles, mixed by integer weights:
+
+    pool.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2, 3, 4), scale_weights=(4, 2, 1, 1))
+
 Reading ``.tif`` is out of scope (no rasterio here): convert once to ``.npz``.
 """
 from __future__ import annotations
@@ -126,9 +131,14 @@ class ScenePool:
         off = self.prefix_offsets[scene]
         return self.prefix[off:off + (h + 1) * (w + 1)].view(h + 1, w + 1)
 
-    def windows(self, tile: int) -> int:
-        """How many windows of side ``tile`` the pool holds."""
-        return int(self._table(tile)[1][-1, 3])
+    def windows(self, tile: int, factor: int = 1) -> int:
+        """How many windows the pool holds for tiles of side ``tile`` at resolution factor ``factor`` (source side ``factor * tile``)."""
+        return int(self._table(int(factor) * int(tile))[1][-1, 3])
+
+    @staticmethod
+    def window_factor(window):
+        """The resolution factor of each row of a ``"window"`` tensor or array [..., 4]: bits 16 .. 18 of the last word, plus 1."""
+        return ((window[..., 3] >> 16) & 7) + 1
 
     def _table(self, tile: int):
         tile = int(tile)
@@ -142,6 +152,14 @@ class ScenePool:
             self._tables[tile] = (torch.from_numpy(t.copy()).to(self.device), t)
         return self._tables[tile]
 
+    def _scaled_tables(self, tile: int, factors):
+        """the tables of the sides ``f * tile`` stacked to [K][S][cols], on the device and on the host"""
+        key = (int(tile), tuple(factors))
+        if key not in self._tables:
+            t = np.stack([self._table(f * int(tile))[1] for f in factors])
+            self._tables[key] = (torch.from_numpy(t.copy()).to(self.device), t)
+        return self._tables[key]
+
     def _outputs(self, B, tile):
         out = {"rgb": torch.empty((B, 3, tile, tile), dtype=torch.float32, device=self.device),
                "nir": torch.empty((B, 1, tile, tile), dtype=torch.float32, device=self.device),
@@ -150,22 +168,50 @@ class ScenePool:
             out["coords"] = torch.empty((B, 2), dtype=torch.float32, device=self.device)
         return out
 
-    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None):
+    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
+               scales=None, scale_weights=None):
         """One batch ``{"rgb" [B,3,T,T], "nir" [B,1,T,T][, "coords" [B,2]]}``, plus ``"window"`` [B,4] int32 = (scene, y0, x0,
-        view | attempt << 8 | exhausted << 31) with ``return_windows``.  Sample b is a function of ``(seed, draw, sample0 + b)`` alone.
-        ``augment``: "d4" (8 views), "flips" (4) or "none".  ``max_invalid``: the most invalid pixels a window may hold (only with
-        ``nodata``); after 8 rejected attempts the last window is returned and bit 31 of its window word is set.  ``out``: the
-        tensors to write into (the dict of an earlier call with ``return_windows`` and the same shapes) instead of new ones."""
+        view | attempt << 8 | (factor - 1) << 16 | exhausted << 31) with ``return_windows``.  Sample b is a function of ``(seed, draw,
+        sample0 + b)`` alone.  ``augment``: "d4" (8 views), "flips" (4) or "none".  ``max_invalid``: the most invalid pixels a window
+        may hold (only with ``nodata``); after 8 rejected attempts the last window is returned and bit 31 of its window word is set.
+        ``out``: the tensors to write into (the dict of an earlier call with ``return_windows`` and the same shapes) instead of new ones.
+        ``scales``: distinct resolution factors in 1 .. 8 (sorted before use), one drawn per sample with the positive integer
+        ``scale_weights`` (default: all 1); the sample is then an f*T window of the source (y0, x0 in source pixels, ``max_invalid``
+        per f x f block, coords of the window's centre) delivered as the T x T tile of its f x f block means.  None: factor 1
+        through ``nirgan_scene_sample``, as ever."""
         if augment not in L.SCENE_VIEWS:
             raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
         B, tile = int(batch_size), int(tile)
-        table, table_host = self._table(tile)
         if B <= 0 or tile <= 0:
             raise ValueError("batch_size and tile must be positive")
-        if int(table_host[-1, 3]) == 0:
-            raise ValueError(f"no scene of the pool holds a {tile} x {tile} window")
         out = out if out is not None else self._outputs(B, tile)
-        d = L.SceneSampleDesc()
+        entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
+        L.call(entry, C.byref(d), _stream(self.device))
+        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
+
+    def _describe(self, out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights):
+        """(name of the entry, its descriptor) of one checked ``sample`` call writing into ``out``"""
+        if scales is None:
+            if scale_weights is not None:
+                raise ValueError("scale_weights without scales")
+            d = L.SceneSampleDesc()
+            table, table_host = self._table(tile)
+            if int(table_host[-1, 3]) == 0:
+                raise ValueError(f"no scene of the pool holds a {tile} x {tile} window")
+            entry = "nirgan_scene_sample"
+        else:
+            d = L.SceneScaledDesc()
+            factors, weights = check_scales(scales, scale_weights)
+            for f in factors:
+                if (f * tile) ** 2 >= 2 ** 31:
+                    raise ValueError(f"scale {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
+            table, table_host = self._scaled_tables(tile, factors)
+            for f, t in zip(factors, table_host):
+                if int(t[-1, 3]) == 0:
+                    raise ValueError(f"scale {f}: no scene of the pool holds a {f * tile} x {f * tile} window")
+            d.K = len(factors)
+            d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
+            entry = "nirgan_scene_sample_scaled"
         d.pool, d.pool_elems, d.dtype, d.S, d.C = self.pool.data_ptr(), self.pool_elems, self.dtype, len(self.shapes), self.C
         d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
         d.prefix, d.prefix_elems = (self.prefix.data_ptr() if self.prefix is not None else None), self.prefix_elems
@@ -176,20 +222,45 @@ class ScenePool:
         d.draw, d.sample0, d.max_invalid = int(draw) & ((1 << 64) - 1), int(sample0) & 0xFFFFFFFF, int(max_invalid)
         d.rgb, d.nir, d.window = out["rgb"].data_ptr(), out["nir"].data_ptr(), out["window"].data_ptr()
         d.coords = out["coords"].data_ptr() if self.geo is not None else None
-        L.call("nirgan_scene_sample", C.byref(d), _stream(self.device))
-        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
+        return entry, d
 
-    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1):
-        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank, world=world)
+    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
+               scale_weights=None):
+        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
+                           world=world, scales=scales, scale_weights=scale_weights)
+
+
+def check_scales(scales, scale_weights=None):
+    """``scales`` / ``scale_weights`` as the entry wants them: (factors rising, their weights); ValueError for what it would refuse"""
+    try:
+        pairs = list(zip(scales, scale_weights if scale_weights is not None else [1] * len(scales), strict=True))
+    except (TypeError, ValueError):
+        raise ValueError("scales must be a sequence of integers and scale_weights, if given, as long as scales") from None
+    if not 1 <= len(pairs) <= L.SCENE_MAX_SCALES:
+        raise ValueError(f"scales must name 1 .. {L.SCENE_MAX_SCALES} factors, got {len(pairs)}")
+    for f, w in pairs:
+        if isinstance(f, bool) or f != int(f) or not 1 <= int(f) <= L.SCENE_MAX_FACTOR:
+            raise ValueError(f"scale {f!r} is not an integer in 1 .. {L.SCENE_MAX_FACTOR}")
+        if isinstance(w, bool) or w != int(w) or int(w) <= 0:
+            raise ValueError(f"scale {f}: the weight {w!r} is not a positive integer")
+    pairs = sorted((int(f), int(w)) for f, w in pairs)
+    factors, weights = tuple(f for f, _ in pairs), tuple(w for _, w in pairs)
+    for a, b in zip(factors, factors[1:]):
+        if a == b:
+            raise ValueError(f"scale {a} is named twice")
+    if sum(weights) >= 2 ** 32:
+        raise ValueError(f"scales {factors}: the weights sum to 2^32 or more")
+    return factors, weights
 
 
 class SceneLoader:
     """A re-iterable of ``steps_per_epoch`` batches per epoch.  Step i of epoch e is ``pool.sample(..., draw=e * steps_per_epoch + i,
-    sample0=rank * batch_size)``.  ``set_epoch(e)`` names the epoch of the next ``iter()`` (``fit`` calls it, so a resumed run
+    sample0=rank * batch_size, scales=..., scale_weights=...)``.  ``set_epoch(e)`` names the epoch of the next ``iter()`` (``fit`` calls it, so a resumed run
     continues where the checkpoint stopped); without it every ``iter()`` moves on by one epoch.  The batches of one loader share their
     tensors: a batch is valid until the next one is drawn, nothing is allocated per step."""
 
-    def __init__(self, pool, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1):
+    def __init__(self, pool, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
+                 scale_weights=None):
         if not 0 <= int(rank) < int(world):
             raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
         if int(steps_per_epoch) <= 0:
@@ -198,6 +269,9 @@ class SceneLoader:
             raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
         self.pool, self.batch_size, self.tile, self.steps_per_epoch = pool, int(batch_size), int(tile), int(steps_per_epoch)
         self.seed, self.augment, self.max_invalid, self.rank, self.world = seed, augment, int(max_invalid), int(rank), int(world)
+        if scales is None and scale_weights is not None:
+            raise ValueError("scale_weights without scales")
+        self.scales, self.scale_weights = (None, None) if scales is None else check_scales(scales, scale_weights)
         self.epoch = 0
         self._buffers = None                                                     # one set of output tensors, made at the first iter()
 
@@ -214,4 +288,4 @@ class SceneLoader:
         for i in range(self.steps_per_epoch):
             yield self.pool.sample(self.batch_size, self.tile, seed=self.seed, draw=epoch * self.steps_per_epoch + i,
                                    sample0=self.rank * self.batch_size, augment=self.augment, max_invalid=self.max_invalid,
-                                   out=self._buffers)
+                                   out=self._buffers, scales=self.scales, scale_weights=self.scale_weights)

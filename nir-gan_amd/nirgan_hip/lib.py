@@ -243,6 +243,13 @@ class SceneSampleDesc(C.Structure):
                 ("max_invalid", i32), ("rgb", fp), ("nir", fp), ("coords", fp), ("window", fp)]
 
 
+SCENE_MAX_SCALES, SCENE_MAX_FACTOR = 8, 8                 # include/nirgan_hip.h: NIRGAN_SCENE_MAX_SCALES / _MAX_FACTOR
+
+
+class SceneScaledDesc(C.Structure):
+    _fields_ = SceneSampleDesc._fields_ + [("K", i32), ("factor", i32 * 8), ("weight", C.c_uint32 * 8)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -305,6 +312,7 @@ PROTOTYPES = {
     "nirgan_raster_lookup": (i32, [C.POINTER(RasterLookupDesc), fp]),
     "nirgan_scene_invalid_prefix": (i32, [C.POINTER(ScenePrefixDesc), fp]),
     "nirgan_scene_sample": (i32, [C.POINTER(SceneSampleDesc), fp]),
+    "nirgan_scene_sample_scaled": (i32, [C.POINTER(SceneScaledDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
