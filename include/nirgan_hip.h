@@ -1266,6 +1266,58 @@ typedef struct {
 } nirgan_scene_scaled_desc;
 int nirgan_scene_sample_scaled(const nirgan_scene_scaled_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * An explicit list of windows cut from device-resident scenes: the gather of the two samplers above without their draw.  It serves
+ * fixed validation sets (a grid of windows cut the same way at every epoch) and gives back the tiles behind a batch: the `window`
+ * rows a sampler wrote can be fed in as they are.
+ *
+ * Pool, geo, band, divisor, rgb, nir, coords: as in nirgan_scene_sample_desc.
+ * table / table_host: int64 [S][NIRGAN_SCENE_TABLE_COLS] in the format of nirgan_scene_sample; columns 0 .. 2 (offset, H_s, W_s) are
+ * read, columns 3 and 4 (cum_windows, prefix offset) are IGNORED: the table of any tile size will do, nothing is drawn or rejected.
+ * window / window_host: int32 [n_windows][4], on the device and the same words in HOST memory; every check reads the host copy.
+ *   row = { s, y0, x0, word }     view = word & 7;   f = ((word >> 16) & 7) + 1;   L = f * T;   y0, x0 in SOURCE pixels
+ * exactly what the two samplers write.  Bits 8 .. 15 (attempt) and bit 31 (exhausted) of the word are ignored; any other set bit is
+ * an argument error.  One call cuts rows first .. first + n - 1; sample i of the call is row first + i.
+ *
+ * At most TWO launches on the stream (the coords, if asked for; the pixels), no host synchronisation, no atomics.
+ *   coords[i] = { (float)(lon0 + ((x0 + L/2) + 0.5) * dlon), (float)(lat0 + ((y0 + L/2) + 0.5) * dlat) }
+ *   L/2 an integer division, then ONE float64 product and ONE float64 sum, not fused, as in nirgan_scene_sample; written only when
+ *   both geo and coords are set.
+ *   Pixels: the Gather of nirgan_scene_sample_scaled, word for word.  D[ch][p][q] = the mean of src_s[band[ch]][y0 + p*f + rr][x0 +
+ *   q*f + e], rr, e = 0 .. f-1: a uint16 pool the exact integer sum and one rounded float32 division by f*f, a float pool the float64
+ *   sum in row-major order of the block from its first value and one rounded float64 division by f*f, converted to float; then
+ *     out[i][ch][j1][j2] = D[ch][j1'][j2'] / divisor                                       (one correctly rounded float32 division)
+ *   with (j1', j2') by the view rule of nirgan_tile_views_expand on the T x T tile; ch 0..2 go to rgb [n][3][T][T], ch 3 to nir
+ *   [n][1][T][T].  For f = 1 this is nirgan_scene_sample's arithmetic.  The result is therefore BITWISE what either sampler
+ *   delivered for the same row.  A call may mix factors and views freely; the kernel (factors to 4, or to 8) is picked from the
+ *   largest factor among the call's rows, read from window_host.  Every output element is written by one thread, the outputs need
+ *   no initialisation, nothing outside them is written.
+ * Argument errors return NIRGAN_ERR_ARG before any launch: a null pointer (d, pool, table, table_host, window, window_host, rgb,
+ * nir); unknown dtype; S <= 0 or C < 4; a band outside 0 .. C-1; tile, n or n*tile*tile outside 1 .. 2^31-1; first < 0 or first + n >
+ * n_windows; divisor == 0 or NaN; a table row with an extent outside 1 .. 2^31-1 or a scene outside the pool; a row in [first,
+ * first + n) with s outside 0 .. S-1, with (f*T)^2 at 2^31 or more, with y0 < 0, x0 < 0, y0 + L > H_s or x0 + L > W_s, or with a stray
+ * bit in its word (the message names the row).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* pool; int64_t pool_elems;
+    int dtype;                            /* NIRGAN_SCENE_U16 or NIRGAN_SCENE_F32 */
+    int S, C;
+    const int64_t* table;                 /* device [S][NIRGAN_SCENE_TABLE_COLS]; columns 0..2 (offset, H, W) are read, 3 and 4 are ignored */
+    const int64_t* table_host;            /* the same table in HOST memory: every check reads it */
+    const double* geo;                    /* device [S][4] or NULL */
+    int band[4];
+    int tile;                             /* side T of the DELIVERED tile */
+    float divisor;
+    const int32_t* window;                /* device [n_windows][4] */
+    const int32_t* window_host;           /* the same words in HOST memory: every check reads them */
+    int64_t n_windows;
+    int64_t first; int n;                 /* this launch cuts windows [first, first + n) */
+    float* rgb;                           /* [n][3][T][T] */
+    float* nir;                           /* [n][1][T][T] */
+    float* coords;                        /* [n][2], or NULL */
+} nirgan_scene_gather_desc;
+int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// Pieces the two scene samplers share (scenepool.hip: nirgan_scene_sample; scenescale.hip: nirgan_scene_sample_scaled): the padded
+// Pieces the scene entries share (scenepool.hip: nirgan_scene_sample; scenescale.hip: nirgan_scene_sample_scaled, nirgan_scene_gather): the padded
 // 64 x 64 LDS block of the gathers, one attempt of the draw on the words of one Philox call, and the coords' unfused product and sum.
 #pragma once
 #include "common.h"
@@ -65,13 +65,13 @@ static inline int sp_check_table(const char* who, const int64_t* table_host, int
     return NIRGAN_OK;
 }
 
-// ... and, once a table is known to hold a window, where its scenes and prefix tables lie
+// ... and, once a table is known to hold a window, where its scenes and prefix tables lie (with_prefix = false: column 4 is not read)
 static inline int sp_check_extents(const char* who, const int64_t* table_host, int S, int C, int64_t pool_elems, const void* prefix,
-                                   int64_t prefix_elems) {
+                                   int64_t prefix_elems, bool with_prefix = true) {
     for (int s = 0; s < S; ++s) {
         const int64_t* r = table_host + int64_t(s) * TC;
         NG_REQUIRE(r[0] >= 0 && r[0] <= pool_elems && r[1] * r[2] <= (pool_elems - r[0]) / C, "%s: scene %d lies outside the pool", who, s);
-        if (r[4] >= 0) {
+        if (with_prefix && r[4] >= 0) {
             NG_REQUIRE(prefix, "%s: scene %d names a prefix table but prefix is null", who, s);
             NG_REQUIRE(r[4] <= prefix_elems && (r[1] + 1) * (r[2] + 1) <= prefix_elems - r[4], "%s: the prefix table of scene %d lies outside prefix_elems", who, s);
         }

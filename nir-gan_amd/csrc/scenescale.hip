@@ -1,4 +1,5 @@
-// Multi-scale training batches from device-resident scenes: nirgan_scene_sample_scaled.
+// Multi-scale training batches from device-resident scenes: nirgan_scene_sample_scaled; and the same gather on a list
+// of windows the caller names: nirgan_scene_gather, at the end of the file.
 //
 // The draw of scenepool.hip with one more decision: sample b takes its resolution factor f from the fourth Philox word of attempt 0,
 // cuts a window of side L = f * T and delivers the T x T tile of the means of its f x f blocks.  Two launches, as there:
@@ -50,7 +51,8 @@ struct ScaledP {
     float divisor;
     uint32_t seed_lo, seed_hi, draw_lo, draw_hi, sample0;
     float* rgb; float* nir; float* coords;
-    int32_t* window;
+    int32_t* window;                     // written by the draw
+    const int32_t* rows;                 // read by the gather: the draw's window, or the caller's list (nirgan_scene_gather)
 };
 
 __global__ __launch_bounds__(256) void scene_scaled_draw_kernel(const ScaledP p) {
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(256) void scene_scaled_gather_kernel(const ScaledP 
         q /= p.nb;
         const int ch = int(q & 3);
         const int64_t b = q >> 2;
-        const int32_t* __restrict__ win = p.window + b * 4;
+        const int32_t* __restrict__ win = p.rows + b * 4;
         const int s = win[0], y0 = win[1], x0 = win[2], view = win[3] & 7, f = ((win[3] >> 16) & 7) + 1;
         int k = 0;
 #pragma unroll
@@ -218,6 +220,20 @@ __global__ __launch_bounds__(256) void scene_scaled_gather_kernel(const ScaledP 
                     }
                 }
         }
+    }
+}
+
+// fmax: the largest factor among the rows the launch reads
+void launch_gather(const ScaledP& p, int dtype, int fmax, hipStream_t st) {
+    const int grid = int(p.nblk < 16384 ? p.nblk : 16384);
+    const bool wide = fmax > 4;
+    const dim3 g(grid), t(256);
+    if (dtype == NIRGAN_SCENE_U16) {
+        if (wide) hipLaunchKernelGGL((scene_scaled_gather_kernel<uint16_t, 8>), g, t, 0, st, p);
+        else hipLaunchKernelGGL((scene_scaled_gather_kernel<uint16_t, 4>), g, t, 0, st, p);
+    } else {
+        if (wide) hipLaunchKernelGGL((scene_scaled_gather_kernel<float, 8>), g, t, 0, st, p);
+        else hipLaunchKernelGGL((scene_scaled_gather_kernel<float, 4>), g, t, 0, st, p);
     }
 }
 
@@ -264,18 +280,78 @@ extern "C" int nirgan_scene_sample_scaled(const nirgan_scene_scaled_desc* d, voi
     p.nblk = int64_t(d->B) * 4 * p.nb * p.nb;
     p.divisor = d->divisor;
     p.seed_lo = d->seed_lo; p.seed_hi = d->seed_hi; p.draw_lo = uint32_t(d->draw); p.draw_hi = uint32_t(d->draw >> 32); p.sample0 = d->sample0;
-    p.rgb = d->rgb; p.nir = d->nir; p.coords = d->geo ? d->coords : nullptr; p.window = d->window;
+    p.rgb = d->rgb; p.nir = d->nir; p.coords = d->geo ? d->coords : nullptr; p.window = d->window; p.rows = d->window;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(scene_scaled_draw_kernel, dim3((d->B + 255) / 256), dim3(256), 0, st, p);
-    const int grid = int(p.nblk < 16384 ? p.nblk : 16384);
-    const bool wide = p.factor[d->K - 1] > 4;                                   // the factors rise: the last is the largest
-    const dim3 g(grid), t(256);
-    if (d->dtype == NIRGAN_SCENE_U16) {
-        if (wide) hipLaunchKernelGGL((scene_scaled_gather_kernel<uint16_t, 8>), g, t, 0, st, p);
-        else hipLaunchKernelGGL((scene_scaled_gather_kernel<uint16_t, 4>), g, t, 0, st, p);
-    } else {
-        if (wide) hipLaunchKernelGGL((scene_scaled_gather_kernel<float, 8>), g, t, 0, st, p);
-        else hipLaunchKernelGGL((scene_scaled_gather_kernel<float, 4>), g, t, 0, st, p);
+    launch_gather(p, d->dtype, p.factor[d->K - 1], st);                         // the factors rise: the last is the largest
+    return nirgan_check_launch(who);
+}
+
+// The gather of the samplers on a list of windows the CALLER names.  The pixels are scene_scaled_gather_kernel's, the
+// same instances: with K = 1 it reads table 0 for every row, whatever the row's factor, and a row's factor only picks the block
+// routine.  The coords are sp_centre's, one thread per row.
+namespace {
+
+struct CentreP {
+    const double* geo; const int32_t* rows; float* coords;
+    int n, T;
+};
+
+__global__ __launch_bounds__(256) void scene_gather_centre_kernel(const CentreP p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n) return;
+    const int32_t* __restrict__ win = p.rows + int64_t(i) * 4;
+    const int f = ((win[3] >> 16) & 7) + 1;
+    sp_centre(p.geo + int64_t(win[0]) * 4, win[1], win[2], f * p.T, p.coords + int64_t(i) * 2);
+}
+
+}  // namespace
+
+extern "C" int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stream) {
+    static const char* who = "scene_gather";
+    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->window && d->window_host && d->rgb && d->nir, "%s: null pointer", who);
+    NG_REQUIRE(d->dtype == NIRGAN_SCENE_U16 || d->dtype == NIRGAN_SCENE_F32, "%s: unknown dtype %d", who, d->dtype);
+    NG_REQUIRE(d->S > 0 && d->C >= 4, "%s: bad pool (S %d, C %d; C must be at least 4)", who, d->S, d->C);
+    for (int k = 0; k < 4; ++k) NG_REQUIRE(d->band[k] >= 0 && d->band[k] < d->C, "%s: band %d outside 0 .. C-1", who, d->band[k]);
+    const int64_t T = d->tile;
+    NG_REQUIRE(d->n > 0 && T > 0 && T * T < LIM31 && T * T * d->n < LIM31, "%s: n, tile or n*tile*tile is not in 1 .. 2^31-1 (n %d, tile %d)", who, d->n, d->tile);
+    NG_REQUIRE(d->first >= 0 && d->n_windows >= d->n && d->first <= d->n_windows - d->n,
+               "%s: first %lld, n %d: the rows are not inside 0 .. n_windows-1 (n_windows %lld)", who, (long long)d->first, d->n, (long long)d->n_windows);
+    NG_REQUIRE(d->divisor == d->divisor && d->divisor != 0.0f, "%s: divisor is 0 or NaN", who);
+    for (int s = 0; s < d->S; ++s) {
+        const int64_t* r = d->table_host + int64_t(s) * TC;
+        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
     }
+    if (int e = sp_check_extents(who, d->table_host, d->S, d->C, d->pool_elems, nullptr, 0, false)) return e;
+    int fmax = 1;
+    for (int64_t i = d->first; i < d->first + d->n; ++i) {
+        const int32_t* w = d->window_host + i * 4;
+        const uint32_t word = uint32_t(w[3]);
+        NG_REQUIRE((word & ~0x8007FF07u) == 0, "%s: row %lld: the word 0x%08x has a bit set outside the view, attempt, factor and exhausted fields", who, (long long)i, word);
+        NG_REQUIRE(w[0] >= 0 && w[0] < d->S, "%s: row %lld: scene %d outside 0 .. S-1", who, (long long)i, w[0]);
+        const int f = int((word >> 16) & 7) + 1;
+        const int64_t L = f * T;                                                // T * T < 2^31: L < 2^19
+        NG_REQUIRE(L * L < LIM31, "%s: row %lld: the window of factor %d, (factor*tile)^2, is 2^31 or more", who, (long long)i, f);
+        const int64_t* r = d->table_host + int64_t(w[0]) * TC;
+        NG_REQUIRE(w[1] >= 0 && w[2] >= 0 && w[1] + L <= r[1] && w[2] + L <= r[2],
+                   "%s: row %lld: the window of side %lld at (%d, %d) is not inside scene %d (%lld x %lld)", who, (long long)i, (long long)L, w[1], w[2], w[0],
+                   (long long)r[1], (long long)r[2]);
+        if (f > fmax) fmax = f;
+    }
+    ScaledP p = {};
+    p.pool = d->pool; p.table = d->table;
+    for (int k = 0; k < 4; ++k) p.band[k] = d->band[k];
+    p.K = 1; p.S = d->S; p.T = d->tile; p.B = d->n;
+    p.nb = (d->tile + SP_B - 1) / SP_B;
+    p.nblk = int64_t(d->n) * 4 * p.nb * p.nb;
+    p.divisor = d->divisor;
+    p.rgb = d->rgb; p.nir = d->nir;
+    p.rows = d->window + d->first * 4;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d->geo && d->coords) {
+        const CentreP c = {d->geo, p.rows, d->coords, d->n, d->tile};
+        hipLaunchKernelGGL(scene_gather_centre_kernel, dim3((d->n + 255) / 256), dim3(256), 0, st, c);
+    }
+    launch_gather(p, d->dtype, fmax, st);
     return nirgan_check_launch(who);
 }

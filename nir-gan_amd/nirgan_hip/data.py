@@ -15,6 +15,15 @@ means (``nirgan_scene_sample_scaled``): a 10 m pool then trains on 
 
     pool.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2, 3, 4), scale_weights=(4, 2, 1, 1))
 
+Validation wants the SAME windows at every epoch: ``grid`` lists a fixed, non-overlapping grid of windows over the scenes (filtered by
+the sampler's nodata rule, at any of the factors), ``gather`` cuts an explicit list of windows through ``nirgan_scene_gather`` -- also
+the ``"window"`` rows of a sampled batch, bitwise as sampled -- and ``grid_loader`` is the re-iterable over a grid that ``fit`` and
+``evaluate_tiles`` take as their validation data.  The training sampler draws ANYWHERE in its pool, so a grid is held
+out only if it comes from a separate pool of held-out scenes:
+
+    val_loader = val_pool.grid_loader(16, 256, factors=(1, 2), max_invalid=0)
+    fit(model, pool.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2)), val_loader, max_epochs=10)
+
 Reading ``.tif`` is out of scope (no rasterio here): convert once to ``.npz``.
 """
 from __future__ import annotations
@@ -228,6 +237,167 @@ class ScenePool:
                scale_weights=None):
         return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
                            world=world, scales=scales, scale_weights=scale_weights)
+
+    def grid(self, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None) -> "WindowList":
+        """A fixed, deterministic list of windows over the scenes, for ``gather`` and ``grid_loader``.  ``factors``:
+        distinct resolution factors in 1 .. 8, used in ascending order; a factor f cuts windows of side L = f * tile.  ``stride``: the
+        step between windows in SOURCE pixels (default L: no overlap; at least 1).  A scene with H >= L and W >= L gives the rows
+        0, stride, 2 * stride, ... <= H - L, with ``cover`` also H - L if that is not the last one already (the far edge is then
+        covered by one overlapping row), and the columns by the same rule; a smaller scene gives nothing.  ``scenes``: the scene
+        indices to use, in this order (default: all).  Order of the list: factor, then scene, then row, then column.  With ``nodata`` a
+        window is kept iff it holds at most ``max_invalid * f * f`` invalid pixels, the scaled sampler's rule; without, all are kept.
+        Every word is ``(f - 1) << 16``: view 0.  The filter runs on the device on the scenes' prefix tables (four gathers per scene
+        and factor) and its verdicts come back in ONE copy, the only synchronisation; a pool without ``nodata`` needs none.
+        ValueError if no window is left."""
+        tile = int(tile)
+        if tile <= 0:
+            raise ValueError("tile must be positive")
+        factors, _ = check_scales(factors)
+        if stride is not None and (isinstance(stride, bool) or stride != int(stride) or int(stride) < 1):
+            raise ValueError(f"stride must be an integer of at least 1 (source pixels), got {stride!r}")
+        if isinstance(max_invalid, bool) or max_invalid != int(max_invalid) or int(max_invalid) < 0:
+            raise ValueError(f"max_invalid must be a non-negative integer, got {max_invalid!r}")
+        ids = list(range(len(self.shapes))) if scenes is None else [int(s) for s in scenes]
+        if any(not 0 <= s < len(self.shapes) for s in ids):
+            raise ValueError(f"scenes must name scenes in 0 .. {len(self.shapes) - 1}, got {list(scenes)}")
+        parts, keeps = [], []
+        for f in factors:
+            side = f * tile
+            if side * side >= 2 ** 31:
+                raise ValueError(f"factor {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
+            step = side if stride is None else int(stride)
+            for s in ids:
+                h, w = self.shapes[s]
+                if h < side or w < side:
+                    continue
+                yy, xx = np.meshgrid(_grid_starts(h, side, step, cover), _grid_starts(w, side, step, cover), indexing="ij")
+                part = np.empty((yy.size, 4), dtype=np.int32)
+                part[:, 0], part[:, 1], part[:, 2], part[:, 3] = s, yy.reshape(-1), xx.reshape(-1), (f - 1) << 16
+                parts.append(part)
+                if self.prefix is not None:
+                    P = self.invalid_prefix(s)
+                    y, x = (torch.from_numpy(part[:, c].astype(np.int64)).to(self.device) for c in (1, 2))
+                    count = P[y + side, x + side].long() - P[y, x + side].long() - P[y + side, x].long() + P[y, x].long()
+                    keeps.append(count <= int(max_invalid) * f * f)
+        rows = np.concatenate(parts) if parts else np.empty((0, 4), dtype=np.int32)
+        if keeps:
+            rows = rows[torch.cat(keeps).cpu().numpy()]                          # the one copy to the host
+        if not len(rows):
+            raise ValueError(f"the grid is empty: no window of tile {tile} at factors {factors} is left on these scenes")
+        return WindowList(rows, self.device)
+
+    def gather(self, windows, tile, *, first=0, count=None, out=None):
+        """``{"rgb" [n,3,T,T], "nir" [n,1,T,T][, "coords" [n,2]]}`` of the rows ``first .. first + count - 1`` (default: to the end) of
+        an explicit list of windows, through ``nirgan_scene_gather``: bitwise what ``sample`` delivered for the same window rows.
+        ``windows``: a ``WindowList`` (of ``grid``), or any int32 tensor or array [n, 4] of (scene, y0, x0, word) rows such as the
+        ``"window"`` of ``sample(..., return_windows=True)``; an array or tensor is wrapped in a ``WindowList`` on every call, which
+        costs a tensor on the device one copy to the host (a synchronisation) -- wrap it once yourself to cut it repeatedly.
+        ``tile``: the side T of the delivered tiles; a row of factor f cuts f*T source pixels.  ``out``: the dict of tensors to write
+        into (same shapes) instead of new ones."""
+        if self.device.type != "cuda" and not L.is_emulated():
+            raise RuntimeError("ScenePool.gather: the pool must live on the MI355X (cuda); the HIP path has no CPU fallback")
+        wl = windows if isinstance(windows, WindowList) else WindowList(windows, self.device)
+        if wl.device.device != self.pool.device:
+            raise ValueError(f"the windows live on {wl.device.device}, the pool on {self.pool.device}")
+        tile, first = int(tile), int(first)
+        n = len(wl) - first if count is None else int(count)
+        if tile <= 0 or first < 0 or n <= 0 or first + n > len(wl):
+            raise ValueError(f"tile must be positive and rows [{first}, {first + n}) a non-empty part of the {len(wl)} windows")
+        if out is None:
+            out = {k: v for k, v in self._outputs(n, tile).items() if k != "window"}
+        for k, shape in (("rgb", (n, 3, tile, tile)), ("nir", (n, 1, tile, tile))) + ((("coords", (n, 2)),) if self.geo is not None else ()):
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.pool.device or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous float32 {shape} tensor on {self.pool.device}")
+        d = L.SceneGatherDesc()
+        table, table_host = self._table(tile)                                    # columns 0 .. 2 are read: the table of any side will do
+        d.pool, d.pool_elems, d.dtype, d.S, d.C = self.pool.data_ptr(), self.pool_elems, self.dtype, len(self.shapes), self.C
+        d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
+        d.geo = self.geo.data_ptr() if self.geo is not None else None
+        d.band = (C.c_int * 4)(*self.bands)
+        d.tile, d.divisor = tile, self.divisor
+        d.window, d.window_host, d.n_windows, d.first, d.n = wl.device.data_ptr(), wl.host.ctypes.data, len(wl), first, n
+        d.rgb, d.nir = out["rgb"].data_ptr(), out["nir"].data_ptr()
+        d.coords = out["coords"].data_ptr() if self.geo is not None else None
+        L.call("nirgan_scene_gather", C.byref(d), _stream(self.device))
+        return {k: out[k] for k in ("rgb", "nir", "coords") if k in out and (k != "coords" or self.geo is not None)}
+
+    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None, rank=0, world=1):
+        """``GridLoader`` over ``grid(tile, ...)``: a fixed validation set.  Rank ``rank`` of ``world`` takes the rows i of the grid
+        with ``i % world == rank``, in order."""
+        if not 0 <= int(rank) < int(world):
+            raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
+        full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover, scenes=scenes)
+        mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
+        return GridLoader(self, mine, batch_size, tile)
+
+
+def _grid_starts(extent, side, step, cover):
+    """0, step, 2 * step, ... <= extent - side, and with ``cover`` extent - side itself if it is not the last"""
+    last = extent - side
+    starts = list(range(0, last + 1, step))
+    if cover and starts[-1] != last:
+        starts.append(last)
+    return np.asarray(starts, dtype=np.int64)
+
+
+class WindowList:
+    """An int32 [n, 4] list of window rows (scene, y0, x0, word) on the device (``.device``, a tensor) with its copy on the host
+    (``.host``, a numpy array): ``nirgan_scene_gather`` checks every row on the host copy and cuts from the device copy.  Built from a
+    host array it uploads (no synchronisation); built from a device tensor it copies to the host ONCE, here.  Both copies are the
+    list's own and are not to be written afterwards."""
+
+    def __init__(self, windows, device):
+        device = torch.device(device)
+        if torch.is_tensor(windows):
+            if windows.dtype != torch.int32 or windows.dim() != 2 or windows.shape[1] != 4:
+                raise ValueError(f"windows must be int32 [n, 4], got {windows.dtype} {tuple(windows.shape)}")
+            self.host = np.ascontiguousarray(windows.detach().cpu().numpy()).copy()
+            self.device = windows.detach().to(device).contiguous().clone()
+        else:
+            a = np.asarray(windows)
+            if a.dtype != np.int32 or a.ndim != 2 or a.shape[1] != 4:
+                raise ValueError(f"windows must be int32 [n, 4], got {a.dtype} {a.shape}")
+            self.host = np.ascontiguousarray(a).copy()
+            self.device = torch.from_numpy(self.host.copy()).to(device)
+
+    def __len__(self):
+        return int(self.host.shape[0])
+
+
+class GridLoader:
+    """A re-iterable over a fixed ``WindowList``: ``ceil(rows / batch_size)`` batches ``{"rgb", "nir"[, "coords"]}`` of
+    ``pool.gather``, the last one possibly smaller, and EVERY ``iter()`` yields bitwise the same batches -- there is no epoch and no
+    ``set_epoch``, so ``fit`` may walk it as often as it likes and epoch 3 is scored on the windows of epoch 30.  The batches are views
+    of one set of tensors made at the first ``iter()``: a batch is valid until the next one is drawn.  A consumer that keeps batches
+    across draws has to clone them; ``evaluate_tiles`` regroups what it is given into its own ``batch_size`` and holds a batch smaller
+    than that back, so give it a ``batch_size`` no larger than the loader's.  ``windows``: this rank's rows; ``factor_of_row``:
+    their resolution factors (numpy).  It has no ``__getitem__``: it is an iterable of batches, not a dataset of samples."""
+
+    def __init__(self, pool, windows, batch_size, tile):
+        if int(batch_size) <= 0 or int(tile) <= 0:
+            raise ValueError("batch_size and tile must be positive")
+        if not len(windows):
+            raise ValueError("a GridLoader needs at least one window (this rank's share of the grid is empty)")
+        self.pool, self.windows, self.batch_size, self.tile = pool, windows, int(batch_size), int(tile)
+        self.factor_of_row = ScenePool.window_factor(windows.host)
+        self._buffers = None
+
+    def __len__(self):
+        return -(-len(self.windows) // self.batch_size)
+
+    def __iter__(self):
+        if self._buffers is None:
+            self._buffers = {k: v for k, v in self.pool._outputs(self.batch_size, self.tile).items() if k != "window"}
+        for first in range(0, len(self.windows), self.batch_size):
+            n = min(self.batch_size, len(self.windows) - first)
+            yield self.pool.gather(self.windows, self.tile, first=first, count=n, out={k: v[:n] for k, v in self._buffers.items()})
+
+    def by_factor(self):
+        """``(f, GridLoader)`` for every factor of the list in ascending order, each over the rows of that factor alone"""
+        for f in sorted(set(self.factor_of_row.tolist())):
+            yield f, GridLoader(self.pool, WindowList(self.windows.host[self.factor_of_row == f], self.windows.device.device),
+                                self.batch_size, self.tile)
 
 
 def check_scales(scales, scale_weights=None):

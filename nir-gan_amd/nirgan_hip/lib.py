@@ -250,6 +250,12 @@ class SceneScaledDesc(C.Structure):
     _fields_ = SceneSampleDesc._fields_ + [("K", i32), ("factor", i32 * 8), ("weight", C.c_uint32 * 8)]
 
 
+class SceneGatherDesc(C.Structure):
+    _fields_ = [("pool", fp), ("pool_elems", i64), ("dtype", i32), ("S", i32), ("C", i32), ("table", fp), ("table_host", fp),
+                ("geo", fp), ("band", i32 * 4), ("tile", i32), ("divisor", f32), ("window", fp), ("window_host", fp),
+                ("n_windows", i64), ("first", i64), ("n", i32), ("rgb", fp), ("nir", fp), ("coords", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -313,6 +319,7 @@ PROTOTYPES = {
     "nirgan_scene_invalid_prefix": (i32, [C.POINTER(ScenePrefixDesc), fp]),
     "nirgan_scene_sample": (i32, [C.POINTER(SceneSampleDesc), fp]),
     "nirgan_scene_sample_scaled": (i32, [C.POINTER(SceneScaledDesc), fp]),
+    "nirgan_scene_gather": (i32, [C.POINTER(SceneGatherDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
