@@ -1318,6 +1318,79 @@ typedef struct {
 } nirgan_scene_gather_desc;
 int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training batches from the part of a pool that is NOT held out: nirgan_scene_sample_scaled with the window drawn from a table of
+ * rectangles of admissible window ORIGINS instead of from whole scenes.  What the draw can name is what the table lists, so a
+ * sample never touches a region the caller left out of the table -- also a sample that runs out of its nodata attempts, which
+ * rejection alone could not promise -- and the draw stays exactly uniform over the windows the table lists.
+ *
+ * pool, pool_elems, dtype, S, C, prefix, prefix_elems, geo, band, tile, B, views, divisor, seed, draw, sample0, max_invalid, rgb,
+ * nir, coords, window, K, factor[8], weight[8]: as in nirgan_scene_scaled_desc, with one exception:
+ * table / table_host: ONE int64 [S][NIRGAN_SCENE_TABLE_COLS] table in the format of nirgan_scene_sample.  Columns 0, 1, 2 and 4
+ * (offset, H_s, W_s, prefix offset) are read; column 3 (cum_windows) is IGNORED, as nirgan_scene_gather ignores it: the table of any
+ * tile size will do.
+ * origins / origins_host: int64 [R][NIRGAN_SCENE_ORIGIN_COLS] on the device and the same rows in HOST memory (every check reads the
+ * host copy, device memory is not read for checks):
+ *     row = { scene, oy, ox, oh, ow, cum }
+ * the windows of side L_k = factor[k] * tile of `scene` whose origin (y0, x0) lies in [oy, oy + oh) x [ox, ox + ow).  Scale k owns
+ * the rows first[k] .. first[k] + count[k] - 1; the scales tile [0, R) in order of k.  cum is the running sum of oh * ow over the
+ * rows of ONE scale: it RESTARTS at every scale, total_k = cum of the last row of scale k.  With one row { s, 0, 0, H_s - L_k + 1,
+ * W_s - L_k + 1, . } per scene that holds a window (scenes too small for L_k left out) the entry is arithmetically
+ * nirgan_scene_sample_scaled, bitwise in rgb, nir, coords and window; with factor = {1} it is nirgan_scene_sample.
+ * Rectangles that OVERLAP are not refused and not looked for: a window under several rectangles is simply drawn that many times as
+ * often.  nirgan_hip.data builds disjoint ones.
+ *
+ * TWO launches on the stream, no host synchronisation, no atomics.
+ *   Draw, one thread per sample b.  The scale k is picked exactly as nirgan_scene_sample_scaled picks it (word 3 of attempt 0, once
+ *   per sample);  f = factor[k];  L = f * T.  Attempt a = 0 .. NIRGAN_SCENE_ATTEMPTS-1, on the words (w0, w1, w2, w3) of that entry:
+ *     u    = w0 | w1 << 32;   idx = floor(u * total_k / 2^64)
+ *     i    = the first row of scale k with cum > idx;   r = idx - cum[i-1], cum[i-1] being 0 for the FIRST row of the scale (not the
+ *            last cum of scale k-1)
+ *     s    = scene_i;   y0 = oy_i + r / ow_i;   x0 = ox_i + r % ow_i;   view = w2 & (views - 1)
+ *     n    = the prefix-table count of the L x L window at (y0, x0) of scene s; 0 where the scene has no table or prefix is NULL
+ *   accepted iff n <= (int64)max_invalid * f * f; if no attempt is, the LAST one is taken and `exhausted` is set.
+ *     window[b] = { s, y0, x0, view | a << 8 | (f - 1) << 16 | exhausted << 31 }          y0, x0 in SOURCE pixels of the scene
+ *     coords[b] = { (float)(lon0 + ((x0 + L/2) + 0.5) * dlon), (float)(lat0 + ((y0 + L/2) + 0.5) * dlat) }      as there
+ *   Gather: the Gather of nirgan_scene_sample_scaled, the same kernel, on the rows the draw wrote: nirgan_scene_gather replays a
+ *   batch bitwise from its window rows.
+ * Argument errors return NIRGAN_ERR_ARG before any launch: everything nirgan_scene_sample_scaled refuses that still applies (a null
+ * pointer -- also origins, origins_host --, dtype, S, C, views, band, B, tile, divisor, max_invalid, negative pool_elems or
+ * prefix_elems, K, factor, weight, Wtot, L_k * L_k at 2^31 or more, a table row with an extent outside 1 .. 2^31-1, a scene outside
+ * the pool, a prefix offset without `prefix` or a prefix table outside prefix_elems); R < 1; a count[k] < 1 (the message names the
+ * factor); first / count not tiling [0, R) in order of k; a row with scene outside 0 .. S-1, oh < 1 or ow < 1, oy < 0 or ox < 0,
+ * oy + oh > H_s - L_k + 1 or ox + ow > W_s - L_k + 1, or a cum that is not the running sum of its scale (the message names the row);
+ * a total_k at 2^62 or more.  These checks are what keeps every window inside its scene.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_SCENE_ORIGIN_COLS 6
+typedef struct {
+    const void* pool; int64_t pool_elems;
+    int dtype;
+    int S, C;
+    const int64_t* table;                 /* device [S][NIRGAN_SCENE_TABLE_COLS]; columns 0, 1, 2, 4 are read, 3 is ignored */
+    const int64_t* table_host;            /* the same table in HOST memory */
+    const int32_t* prefix; int64_t prefix_elems;
+    const double* geo;
+    int band[4];
+    int tile, B, views;                   /* tile: the side T of the DELIVERED tile */
+    float divisor;
+    uint32_t seed_lo, seed_hi;
+    uint64_t draw;
+    uint32_t sample0;
+    int max_invalid;                      /* invalid source pixels allowed per f x f block's worth of window area */
+    float* rgb;                           /* [B][3][T][T] */
+    float* nir;                           /* [B][1][T][T] */
+    float* coords;                        /* [B][2], or NULL */
+    int32_t* window;                      /* [B][4] */
+    int K;                                /* 1 .. NIRGAN_SCENE_MAX_SCALES */
+    int factor[8];
+    uint32_t weight[8];
+    const int64_t* origins;               /* device [R][NIRGAN_SCENE_ORIGIN_COLS] = { scene, oy, ox, oh, ow, cum } */
+    const int64_t* origins_host;          /* the same rows in HOST memory: every check reads them */
+    int R;                                /* rows of all scales together */
+    int first[8], count[8];               /* scale k owns rows first[k] .. first[k] + count[k] - 1 */
+} nirgan_scene_origins_desc;
+int nirgan_scene_sample_origins(const nirgan_scene_origins_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

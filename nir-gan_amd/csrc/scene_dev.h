@@ -1,5 +1,6 @@
-// Pieces the scene entries share (scenepool.hip: nirgan_scene_sample; scenescale.hip: nirgan_scene_sample_scaled, nirgan_scene_gather): the padded
-// 64 x 64 LDS block of the gathers, one attempt of the draw on the words of one Philox call, and the coords' unfused product and sum.
+// Pieces the scene entries share (scenepool.hip: nirgan_scene_sample; scenescale.hip: nirgan_scene_sample_scaled, nirgan_scene_gather,
+// nirgan_scene_sample_origins): the padded 64 x 64 LDS block of the gathers, one attempt of the draw on the words of one Philox call
+// (over whole scenes: sp_attempt; over a table of origin rectangles: so_attempt), and the coords' unfused product and sum.
 #pragma once
 #include "common.h"
 #include "philox_dev.h"
@@ -39,6 +40,37 @@ __device__ __forceinline__ int64_t sp_attempt(const uint32_t w[4], const int64_t
     if (prefix && row[4] >= 0) {
         const int32_t* __restrict__ P = prefix + row[4];
         const int64_t ld = W + 1;
+        n = int64_t(P[(y0 + T) * ld + x0 + T]) - P[y0 * ld + x0 + T] - P[(y0 + T) * ld + x0] + P[y0 * ld + x0];
+    }
+    return n;
+}
+
+constexpr int OC = NIRGAN_SCENE_ORIGIN_COLS;
+
+// One attempt of nirgan_scene_sample_origins: the window of side T that the words w name among the `total` origins of the `count`
+// rows {scene, oy, ox, oh, ow, cum} at `rows` (the rows of ONE scale, cum running from its first row), and the number of invalid
+// pixels it holds (0 without a prefix table).  table: the [S][TC] scene table (W_s and the prefix offset are read).
+__device__ __forceinline__ int64_t so_attempt(const uint32_t w[4], const int64_t* __restrict__ table, const int64_t* __restrict__ rows, int count,
+                                              const int32_t* __restrict__ prefix, int T, int64_t total, int views, int& s, int& y0, int& x0, int& view) {
+    const uint64_t u = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+    const int64_t idx = int64_t(__umul64hi(u, uint64_t(total)));                // < total
+    int lo = 0, hi = count - 1;                                                 // the first row with cum > idx (cum[count-1] = total > idx)
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (rows[int64_t(mid) * OC + 5] > idx) hi = mid; else lo = mid + 1;
+    }
+    const int64_t* __restrict__ row = rows + int64_t(lo) * OC;
+    const int64_t r = idx - (lo > 0 ? row[5 - OC] : 0);
+    const int64_t ow = row[4];
+    s = int(row[0]);
+    y0 = int(row[1] + r / ow);
+    x0 = int(row[2] + r % ow);
+    view = int(w[2] & uint32_t(views - 1));
+    const int64_t* __restrict__ scene = table + int64_t(s) * TC;
+    int64_t n = 0;
+    if (prefix && scene[4] >= 0) {
+        const int32_t* __restrict__ P = prefix + scene[4];
+        const int64_t ld = scene[2] + 1;
         n = int64_t(P[(y0 + T) * ld + x0 + T]) - P[y0 * ld + x0 + T] - P[(y0 + T) * ld + x0] + P[y0 * ld + x0];
     }
     return n;

@@ -1,5 +1,6 @@
 // Multi-scale training batches from device-resident scenes: nirgan_scene_sample_scaled; and the same gather on a list
-// of windows the caller names: nirgan_scene_gather, at the end of the file.
+// of windows the caller names: nirgan_scene_gather; and the draw from a table of rectangles of window origins with the
+// same gather behind it: nirgan_scene_sample_origins, at the end of the file.
 //
 // The draw of scenepool.hip with one more decision: sample b takes its resolution factor f from the fourth Philox word of attempt 0,
 // cuts a window of side L = f * T and delivers the T x T tile of the means of its f x f blocks.  Two launches, as there:
@@ -353,5 +354,139 @@ extern "C" int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stre
         hipLaunchKernelGGL(scene_gather_centre_kernel, dim3((d->n + 255) / 256), dim3(256), 0, st, c);
     }
     launch_gather(p, d->dtype, fmax, st);
+    return nirgan_check_launch(who);
+}
+
+// The draw from a table of rectangles of window origins: nirgan_scene_sample_origins.  Its own parameter block and its
+// own attempt (so_attempt of scene_dev.h); the scale is picked as scene_scaled_draw_kernel picks it, the window word and the coords
+// are written as there, and the pixels are scene_scaled_gather_kernel's on the rows the draw wrote, launched as nirgan_scene_gather
+// launches it: K = 1, the one scene table for every row.
+namespace {
+
+struct OriginsP {
+    const int64_t* table;                // [S][TC]: W_s and the prefix offset are read
+    const int64_t* origins;              // [R][OC]
+    const int32_t* prefix;
+    const double* geo;
+    int64_t total[MAXK];                 // origins of scale k: the cum of its last row
+    int first[MAXK], count[MAXK];
+    int factor[MAXK];
+    uint32_t cumw[MAXK], wtot;
+    int K, T, B, views, max_invalid;
+    uint32_t seed_lo, seed_hi, draw_lo, draw_hi, sample0;
+    float* coords;
+    int32_t* window;
+};
+
+__global__ __launch_bounds__(256) void scene_origins_draw_kernel(const OriginsP p) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.B) return;
+    uint32_t w[4];
+    philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), 0u, p.seed_lo, p.seed_hi, w);
+    const uint32_t pick = uint32_t((uint64_t(w[3]) * uint64_t(p.wtot)) >> 32);             // floor(w3 * Wtot / 2^32) < Wtot
+    int f = p.factor[0], first = p.first[0], count = p.count[0];
+    int64_t total = p.total[0];
+#pragma unroll
+    for (int j = 1; j < MAXK; ++j)       // cumw rises: the last j with cumw[j-1] <= pick is the first with cumw[j] > pick
+        if (j < p.K && p.cumw[j - 1] <= pick) { f = p.factor[j]; first = p.first[j]; count = p.count[j]; total = p.total[j]; }
+    const int L = f * p.T;
+    const int64_t* __restrict__ rows = p.origins + int64_t(first) * OC;
+    const int64_t most = int64_t(p.max_invalid) * f * f;
+    int s = 0, y0 = 0, x0 = 0, view = 0, a = 0;
+    bool ok = false;
+    for (; a < NIRGAN_SCENE_ATTEMPTS; ++a) {
+        if (a > 0) philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), uint32_t(a), p.seed_lo, p.seed_hi, w);
+        const int64_t n = so_attempt(w, p.table, rows, count, p.prefix, L, total, p.views, s, y0, x0, view);
+        if (n <= most) { ok = true; break; }
+    }
+    if (!ok) a = NIRGAN_SCENE_ATTEMPTS - 1;
+    int32_t* __restrict__ o = p.window + int64_t(b) * 4;
+    o[0] = s; o[1] = y0; o[2] = x0;
+    o[3] = int32_t(uint32_t(view) | (uint32_t(a) << 8) | (uint32_t(f - 1) << 16) | (ok ? 0u : 0x80000000u));
+    if (p.geo && p.coords) sp_centre(p.geo + int64_t(s) * 4, y0, x0, L, p.coords + int64_t(b) * 2);
+}
+
+}  // namespace
+
+extern "C" int nirgan_scene_sample_origins(const nirgan_scene_origins_desc* d, void* stream) {
+    static const char* who = "scene_sample_origins";
+    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->origins && d->origins_host && d->rgb && d->nir && d->window, "%s: null pointer", who);
+    NG_REQUIRE(d->dtype == NIRGAN_SCENE_U16 || d->dtype == NIRGAN_SCENE_F32, "%s: unknown dtype %d", who, d->dtype);
+    NG_REQUIRE(d->S > 0 && d->C >= 4, "%s: bad pool (S %d, C %d; C must be at least 4)", who, d->S, d->C);
+    NG_REQUIRE(d->views == 1 || d->views == 4 || d->views == 8, "%s: views %d is not 1, 4 or 8", who, d->views);
+    for (int k = 0; k < 4; ++k) NG_REQUIRE(d->band[k] >= 0 && d->band[k] < d->C, "%s: band %d outside 0 .. C-1", who, d->band[k]);
+    const int64_t T = d->tile;
+    NG_REQUIRE(d->B > 0 && T > 0 && T * T < LIM31 && T * T * d->B < LIM31, "%s: B, tile or B*tile*tile is not in 1 .. 2^31-1 (B %d, tile %d)", who, d->B, d->tile);
+    NG_REQUIRE(d->divisor == d->divisor && d->divisor != 0.0f, "%s: divisor is 0 or NaN", who);
+    NG_REQUIRE(d->max_invalid >= 0, "%s: negative max_invalid", who);
+    NG_REQUIRE(d->pool_elems >= 0 && d->prefix_elems >= 0, "%s: negative pool_elems or prefix_elems", who);
+    NG_REQUIRE(d->K >= 1 && d->K <= MAXK, "%s: K %d outside 1 .. %d", who, d->K, MAXK);
+    OriginsP p;
+    uint64_t wtot = 0;
+    for (int k = 0; k < d->K; ++k) {
+        const int f = d->factor[k];
+        NG_REQUIRE(f >= 1 && f <= MAXF, "%s: factor %d outside 1 .. %d", who, f, MAXF);
+        NG_REQUIRE(k == 0 || f > d->factor[k - 1], "%s: the factors are not strictly increasing (%d after %d)", who, f, d->factor[k - 1]);
+        NG_REQUIRE(d->weight[k] > 0, "%s: the weight of factor %d is 0", who, f);
+        wtot += d->weight[k];
+        NG_REQUIRE(wtot < (uint64_t(1) << 32), "%s: the weights sum to 2^32 or more", who);
+        NG_REQUIRE(f * T * f * T < LIM31, "%s: the window of factor %d, (factor*tile)^2, is 2^31 or more", who, f);
+        p.factor[k] = f;
+        p.cumw[k] = uint32_t(wtot);
+    }
+    for (int s = 0; s < d->S; ++s) {
+        const int64_t* r = d->table_host + int64_t(s) * TC;
+        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
+    }
+    if (int e = sp_check_extents(who, d->table_host, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
+    NG_REQUIRE(d->R >= 1, "%s: R %d: the origin table has no row", who, d->R);
+    int64_t next = 0;
+    for (int k = 0; k < d->K; ++k) {
+        NG_REQUIRE(d->count[k] >= 1, "%s: factor %d owns no row of the origin table (count %d): no admissible window of side %lld", who, p.factor[k],
+                   d->count[k], (long long)(p.factor[k] * T));
+        NG_REQUIRE(d->first[k] == next, "%s: first / count do not tile 0 .. R-1 in order (scale %d starts at row %d, not %lld)", who, k, d->first[k], (long long)next);
+        next += d->count[k];
+        NG_REQUIRE(next <= d->R, "%s: first / count do not tile 0 .. R-1 in order (scale %d ends past R %d)", who, k, d->R);
+    }
+    NG_REQUIRE(next == d->R, "%s: first / count do not tile 0 .. R-1 in order (they end at row %lld, R %d)", who, (long long)next, d->R);
+    for (int k = 0; k < d->K; ++k) {
+        const int64_t L = p.factor[k] * T;
+        int64_t total = 0;
+        for (int i = d->first[k]; i < d->first[k] + d->count[k]; ++i) {
+            const int64_t* o = d->origins_host + int64_t(i) * OC;
+            NG_REQUIRE(o[0] >= 0 && o[0] < d->S, "%s: row %d: scene %lld outside 0 .. S-1", who, i, (long long)o[0]);
+            const int64_t* r = d->table_host + o[0] * TC;
+            const int64_t ny = r[1] - L + 1, nx = r[2] - L + 1;                   // origins of the whole scene; not positive if it holds no window
+            NG_REQUIRE(o[3] >= 1 && o[4] >= 1, "%s: row %d: an extent (oh %lld, ow %lld) below 1", who, i, (long long)o[3], (long long)o[4]);
+            NG_REQUIRE(o[1] >= 0 && o[2] >= 0, "%s: row %d: a negative origin (oy %lld, ox %lld)", who, i, (long long)o[1], (long long)o[2]);
+            NG_REQUIRE(o[1] <= ny && o[3] <= ny - o[1] && o[2] <= nx && o[4] <= nx - o[2],
+                       "%s: row %d: windows of side %lld from origins (%lld, %lld) + (%lld, %lld) are not inside scene %lld (%lld x %lld)", who, i, (long long)L,
+                       (long long)o[1], (long long)o[2], (long long)o[3], (long long)o[4], (long long)o[0], (long long)r[1], (long long)r[2]);
+            total += o[3] * o[4];                                                 // each term below 2^62: the sum cannot wrap before the bound
+            NG_REQUIRE(total < (int64_t(1) << 62), "%s: factor %d has 2^62 origins or more", who, p.factor[k]);
+            NG_REQUIRE(o[5] == total, "%s: row %d: cum is not the running sum of oh*ow of factor %d", who, i, p.factor[k]);
+        }
+        p.total[k] = total;
+        p.first[k] = d->first[k];
+        p.count[k] = d->count[k];
+    }
+    p.wtot = uint32_t(wtot);
+    for (int k = d->K; k < MAXK; ++k) { p.factor[k] = 0; p.cumw[k] = 0; p.total[k] = 0; p.first[k] = 0; p.count[k] = 0; }
+    p.table = d->table; p.origins = d->origins; p.prefix = d->prefix; p.geo = d->geo;
+    p.K = d->K; p.T = d->tile; p.B = d->B; p.views = d->views; p.max_invalid = d->max_invalid;
+    p.seed_lo = d->seed_lo; p.seed_hi = d->seed_hi; p.draw_lo = uint32_t(d->draw); p.draw_hi = uint32_t(d->draw >> 32); p.sample0 = d->sample0;
+    p.coords = d->geo ? d->coords : nullptr; p.window = d->window;
+    ScaledP g = {};                                                             // the gather's block, as nirgan_scene_gather fills it
+    g.pool = d->pool; g.table = d->table;
+    for (int k = 0; k < 4; ++k) g.band[k] = d->band[k];
+    g.K = 1; g.S = d->S; g.T = d->tile; g.B = d->B;
+    g.nb = (d->tile + SP_B - 1) / SP_B;
+    g.nblk = int64_t(d->B) * 4 * g.nb * g.nb;
+    g.divisor = d->divisor;
+    g.rgb = d->rgb; g.nir = d->nir;
+    g.rows = d->window;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(scene_origins_draw_kernel, dim3((d->B + 255) / 256), dim3(256), 0, st, p);
+    launch_gather(g, d->dtype, p.factor[d->K - 1], st);                         // the factors rise: the last is the largest
     return nirgan_check_launch(who);
 }

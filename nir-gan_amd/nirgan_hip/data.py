@@ -19,10 +19,19 @@ Validation wants the SAME windows at every epoch: ``grid`` lists a fixed, non-ov
 the sampler's nodata rule, at any of the factors), ``gather`` cuts an explicit list of windows through ``nirgan_scene_gather`` -- also
 the ``"window"`` rows of a sampled batch, bitwise as sampled -- and ``grid_loader`` is the re-iterable over a grid that ``fit`` and
 ``evaluate_tiles`` take as their validation data.  The training sampler draws ANYWHERE in its pool, so a grid is held
-out only if it comes from a separate pool of held-out scenes:
+out only if it comes from a separate pool of held-out scenes, or from the two halves of ``pool.split(...)``:
 
     val_loader = val_pool.grid_loader(16, 256, factors=(1, 2), max_invalid=0)
     fit(model, pool.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2)), val_loader, max_epochs=10)
+
+``split`` holds rectangles of a pool's scenes out (``split_blocks`` picks them on a block lattice): ``split.train`` samples through
+``nirgan_scene_sample_origins``, whose draw runs over a table of the admissible window ORIGINS -- no window it can name touches a
+held-out rectangle (widened by ``guard`` pixels), whatever the nodata attempts do, and every admissible window is equally likely;
+``split.val`` lists the grid windows lying fully inside one held-out rectangle.  Both halves share the pool's buffers:
+
+    split = pool.split_blocks(512, 0.2, seed=3, guard=16)
+    fit(model, split.train.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2)),
+        split.val.grid_loader(16, 256, factors=(1, 2)), max_epochs=10)
 
 Reading ``.tif`` is out of scope (no rasterio here): convert once to ``.npz``.
 """
@@ -330,6 +339,292 @@ class ScenePool:
         full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover, scenes=scenes)
         mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
         return GridLoader(self, mine, batch_size, tile)
+
+    def split(self, val, guard=0) -> "PoolSplit":
+        """Hold rectangles of the scenes out of training.  ``val``: ``(scene, y0, x0, h, w)`` rectangles in source pixels,
+        each inside its scene, pairwise disjoint (ValueError otherwise); an empty list holds nothing out.  ``guard`` >= 0: no training
+        window comes closer than ``guard`` pixels to a rectangle.  The ``PoolSplit``'s ``.train`` and ``.val`` share this pool's
+        buffers, nothing is copied."""
+        return PoolSplit(self, val, guard)
+
+    def split_blocks(self, block, val_fraction, seed, guard=0) -> "PoolSplit":
+        """``split`` on a lattice of ``block`` x ``block`` cells.  The candidates are the FULL cells (s, i, j), i < H_s // block, j < W_s
+        // block (partial cells at the far edges always train); ``n = max(1, int(val_fraction * cells + 0.5))`` of them are held out:
+        those with the smallest ``block_key(seed, s, i, j)``, ties broken by (s, i, j) -- pure Python integers, the same cells on every
+        platform.  Adjacent cells of a block row are merged into one rectangle, and runs over the same columns in consecutive block
+        rows are stacked."""
+        if isinstance(block, bool) or block != int(block) or int(block) < 1:
+            raise ValueError(f"block must be a positive integer, got {block!r}")
+        if not 0.0 < float(val_fraction) < 1.0:
+            raise ValueError(f"val_fraction must lie strictly between 0 and 1, got {val_fraction!r}")
+        return PoolSplit(self, block_rectangles(self.shapes, int(block), float(val_fraction), int(seed)), guard)
+
+
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x: int) -> int:
+    """one step of SplitMix64 from state ``x``: the standard constants and shifts, Python integers mod 2^64"""
+    z = (x + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def block_key(seed: int, s: int, i: int, j: int) -> int:
+    """the key of cell (i, j) of scene s in ``split_blocks``: splitmix64(splitmix64(splitmix64((seed mod 2^64) ^ s) ^ i) ^ j)"""
+    return splitmix64(splitmix64(splitmix64((int(seed) & _M64) ^ s) ^ i) ^ j)
+
+
+def block_rectangles(shapes, block, val_fraction, seed):
+    """the held-out rectangles ``(scene, y0, x0, h, w)`` of ``ScenePool.split_blocks``, sorted by (scene, y0, x0)"""
+    cells = [(s, i, j) for s, (h, w) in enumerate(shapes) for i in range(h // block) for j in range(w // block)]
+    if not cells:
+        raise ValueError(f"no scene holds a full {block} x {block} block")
+    n = max(1, int(val_fraction * len(cells) + 0.5))
+    held = set(sorted(cells, key=lambda c: (block_key(seed, *c), c))[:n])
+    out = []
+    for s, (h, w) in enumerate(shapes):
+        open_runs = {}                                                           # (j0, j1) -> the block row the stack began at
+        for i in range(h // block + 1):                                          # one row past the last closes what is open
+            runs, j = [], 0
+            while j < w // block:
+                if (s, i, j) in held:
+                    j0 = j
+                    while (s, i, j + 1) in held:
+                        j += 1
+                    runs.append((j0, j + 1))
+                j += 1
+            for run in [r for r in open_runs if r not in runs]:
+                i0 = open_runs.pop(run)
+                out.append((s, i0 * block, run[0] * block, (i - i0) * block, (run[1] - run[0]) * block))
+            for run in runs:
+                open_runs.setdefault(run, i)
+    return sorted(out)
+
+
+def origin_rectangles(shape, side, held, guard=0):
+    """The admissible window origins of ONE scene as disjoint rectangles ``(oy, ox, oh, ow)``: ``[0, H - side] x [0, W - side]`` minus
+    the origins whose ``side`` x ``side`` window touches one of the rectangles ``held`` = ``(y0, x0, h, w)`` widened by ``guard``.  A
+    sweep over y-slabs: the breakpoints of the forbidden origin rectangles cut the origin rows into slabs, each slab keeps the
+    complement of its forbidden x-intervals, and consecutive slabs with the same intervals are merged.  Order: by oy, then ox."""
+    H, W = shape
+    ny, nx = H - side + 1, W - side + 1
+    if ny < 1 or nx < 1:
+        return []
+    forbidden = []                                                               # half-open origin rectangles (ya, yb, xa, xb)
+    for ry, rx, rh, rw in held:
+        ya, yb = max(0, ry - guard - side + 1), min(ny, ry + rh + guard)
+        xa, xb = max(0, rx - guard - side + 1), min(nx, rx + rw + guard)
+        if ya < yb and xa < xb:
+            forbidden.append((ya, yb, xa, xb))
+    cuts = sorted({0, ny} | {y for f in forbidden for y in f[:2]})
+    slabs = []                                                                   # [y start, y end, free x-intervals]
+    for ya, yb in zip(cuts, cuts[1:]):
+        free, x = [], 0
+        for xa, xb in sorted((f[2], f[3]) for f in forbidden if f[0] <= ya < f[1]):
+            if xa > x:
+                free.append((x, xa))
+            x = max(x, xb)
+        if x < nx:
+            free.append((x, nx))
+        if slabs and slabs[-1][1] == ya and slabs[-1][2] == free:
+            slabs[-1][1] = yb
+        else:
+            slabs.append([ya, yb, free])
+    return [(ya, xa, yb - ya, xb - xa) for ya, yb, free in slabs for xa, xb in free]
+
+
+class PoolSplit:
+    """A pool with rectangles held out (``ScenePool.split`` / ``split_blocks``).  ``rectangles``: the held-out ``(scene,
+    y0, x0, h, w)`` as given; ``guard``; ``train``: the sampler of everything else (``SplitTrain``); ``val``: the grid inside the
+    rectangles (``SplitVal``).  Both read the pool's own device buffers."""
+
+    def __init__(self, pool, val, guard=0):
+        if isinstance(guard, bool) or guard != int(guard) or int(guard) < 0:
+            raise ValueError(f"guard must be a non-negative integer (source pixels), got {guard!r}")
+        rects = []
+        for r in val:
+            try:
+                s, y0, x0, h, w = (int(v) for v in r)
+                exact = all(v == int(v) for v in r)
+            except (TypeError, ValueError):
+                raise ValueError(f"a held-out rectangle is (scene, y0, x0, h, w) in integers, got {r!r}") from None
+            if not exact:
+                raise ValueError(f"a held-out rectangle is (scene, y0, x0, h, w) in integers, got {r!r}")
+            if not 0 <= s < len(pool.shapes):
+                raise ValueError(f"rectangle {r!r}: scene {s} outside 0 .. {len(pool.shapes) - 1}")
+            H, W = pool.shapes[s]
+            if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+                raise ValueError(f"rectangle {r!r} is empty or not inside scene {s} ({H} x {W})")
+            for o in rects:
+                if o[0] == s and y0 < o[1] + o[3] and o[1] < y0 + h and x0 < o[2] + o[4] and o[2] < x0 + w:
+                    raise ValueError(f"rectangles {o!r} and {(s, y0, x0, h, w)!r} overlap")
+            rects.append((s, y0, x0, h, w))
+        self.pool, self.rectangles, self.guard = pool, rects, int(guard)
+        self.train, self.val = SplitTrain(self), SplitVal(self)
+
+    def overlap(self, windows, tile, guard=0) -> np.ndarray:
+        """The audit, on the host: int64 [n], for each row ``(scene, y0, x0, word)`` of ``windows`` (a ``WindowList``, tensor or array
+        [n, 4]) the number of pixels of its ``f * tile`` window that lie inside a held-out rectangle, each widened by ``guard`` pixels
+        on every side -- 0 for every row ``train`` draws (also with this split's own guard), ``(f * tile)^2`` for every row of
+        ``val.grid``."""
+        rows = windows.host if isinstance(windows, WindowList) else windows
+        rows = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows).astype(np.int64).reshape(-1, 4)
+        side = (((rows[:, 3] >> 16) & 7) + 1) * int(tile)
+        guard = int(guard)
+        out = np.zeros(len(rows), dtype=np.int64)
+        for s, y0, x0, h, w in self.rectangles:
+            dy = np.minimum(rows[:, 1] + side, y0 + h + guard) - np.maximum(rows[:, 1], y0 - guard)
+            dx = np.minimum(rows[:, 2] + side, x0 + w + guard) - np.maximum(rows[:, 2], x0 - guard)
+            out += np.where(rows[:, 0] == s, np.clip(dy, 0, None) * np.clip(dx, 0, None), 0)
+        return out
+
+
+class SplitTrain:
+    """The training half of a ``PoolSplit``: ``sample`` / ``loader`` with ``ScenePool``'s signatures, through
+    ``nirgan_scene_sample_origins``.  The draw runs over a table of rectangles of admissible window origins, built on the host by
+    ``origin_rectangles`` once per ``(tile, factors)``: it is exactly uniform over the admissible windows and cannot name a window
+    that touches a held-out rectangle widened by the guard."""
+
+    def __init__(self, split):
+        self.split, self.pool, self.device = split, split.pool, split.pool.device
+        self._origins = {}                                                       # (tile, factors) -> (device rows, host rows, first, count)
+
+    def _outputs(self, B, tile):
+        return self.pool._outputs(B, tile)
+
+    def _table(self, tile, factors):
+        key = (int(tile), tuple(factors))
+        if key not in self._origins:
+            rows, first, count = [], [], []
+            held = {s: [r[1:] for r in self.split.rectangles if r[0] == s] for s in range(len(self.pool.shapes))}
+            for f in key[1]:
+                side, cum = f * key[0], 0
+                if side * side >= 2 ** 31:
+                    raise ValueError(f"scale {f}: the window ({f} * {key[0]})^2 has 2^31 pixels or more")
+                first.append(len(rows))
+                for s, shape in enumerate(self.pool.shapes):
+                    for oy, ox, oh, ow in origin_rectangles(shape, side, held[s], self.split.guard):
+                        cum += oh * ow
+                        rows.append((s, oy, ox, oh, ow, cum))
+                count.append(len(rows) - first[-1])
+                if not count[-1]:
+                    raise ValueError(f"scale {f}: no {side} x {side} window of the pool lies outside the held-out rectangles (guard {self.split.guard})")
+            host = np.asarray(rows, dtype=np.int64).reshape(-1, L.SCENE_ORIGIN_COLS)
+            self._origins[key] = (torch.from_numpy(host.copy()).to(self.device), host, tuple(first), tuple(count))
+        return self._origins[key]
+
+    def origins(self, tile, factor=1) -> np.ndarray:
+        """the host rows ``(scene, oy, ox, oh, ow, cum)`` of the origin table for windows of side ``factor * tile`` (a copy)"""
+        return self._table(tile, (int(factor),))[1].copy()
+
+    def windows(self, tile, factor=1) -> int:
+        """how many windows of side ``factor * tile`` are admissible"""
+        return int(self._table(tile, (int(factor),))[1][-1, 5])
+
+    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
+               scales=None, scale_weights=None):
+        """``ScenePool.sample`` on the admissible windows.  ``scales=None``: factor 1, through the same entry.  After 8 rejected
+        nodata attempts the last window is returned with bit 31 set, as there -- it is an admissible window all the same."""
+        if augment not in L.SCENE_VIEWS:
+            raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
+        B, tile = int(batch_size), int(tile)
+        if B <= 0 or tile <= 0:
+            raise ValueError("batch_size and tile must be positive")
+        out = out if out is not None else self._outputs(B, tile)
+        entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
+        L.call(entry, C.byref(d), _stream(self.device))
+        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
+
+    def _describe(self, out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights):
+        """(name of the entry, its descriptor) of one checked ``sample`` call writing into ``out``"""
+        if scales is None and scale_weights is not None:
+            raise ValueError("scale_weights without scales")
+        factors, weights = check_scales(scales, scale_weights) if scales is not None else ((1,), (1,))
+        origins, origins_host, first, count = self._table(tile, factors)
+        pool = self.pool
+        d = L.SceneOriginsDesc()
+        table, table_host = pool._table(tile)                                    # columns 0, 1, 2, 4 are read: the table of any side will do
+        d.pool, d.pool_elems, d.dtype, d.S, d.C = pool.pool.data_ptr(), pool.pool_elems, pool.dtype, len(pool.shapes), pool.C
+        d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
+        d.prefix, d.prefix_elems = (pool.prefix.data_ptr() if pool.prefix is not None else None), pool.prefix_elems
+        d.geo = pool.geo.data_ptr() if pool.geo is not None else None
+        d.band = (C.c_int * 4)(*pool.bands)
+        d.tile, d.B, d.views, d.divisor = tile, B, L.SCENE_VIEWS[augment], pool.divisor
+        d.seed_lo, d.seed_hi = split_seed(seed)
+        d.draw, d.sample0, d.max_invalid = int(draw) & ((1 << 64) - 1), int(sample0) & 0xFFFFFFFF, int(max_invalid)
+        d.rgb, d.nir, d.window = out["rgb"].data_ptr(), out["nir"].data_ptr(), out["window"].data_ptr()
+        d.coords = out["coords"].data_ptr() if pool.geo is not None else None
+        d.K = len(factors)
+        d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
+        d.origins, d.origins_host, d.R = origins.data_ptr(), origins_host.ctypes.data, len(origins_host)
+        d.first, d.count = (C.c_int * 8)(*first), (C.c_int * 8)(*count)
+        return "nirgan_scene_sample_origins", d
+
+    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
+               scale_weights=None):
+        """``SceneLoader`` over this half: it only asks its pool for ``_outputs`` and ``sample``"""
+        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
+                           world=world, scales=scales, scale_weights=scale_weights)
+
+
+class SplitVal:
+    """The validation half of a ``PoolSplit``: ``grid`` lists the windows lying FULLY inside one held-out rectangle, ``gather`` and
+    ``grid_loader`` cut them from the pool's buffers (``nirgan_scene_gather``, ``GridLoader``)."""
+
+    def __init__(self, split):
+        self.split, self.pool, self.device = split, split.pool, split.pool.device
+
+    def grid(self, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True) -> "WindowList":
+        """``ScenePool.grid`` with every held-out rectangle in the place of a scene: a rectangle of h x w pixels at (y0, x0) with h >= L
+        and w >= L gives the rows y0 + 0, stride, 2 * stride, ... <= y0 + h - L (with ``cover`` also y0 + h - L) and the columns by the
+        same rule.  Order: factor, then rectangle as given to ``split``, then row, then column.  The nodata filter is the grid's own.
+        ValueError if no window is left."""
+        pool, tile = self.pool, int(tile)
+        if tile <= 0:
+            raise ValueError("tile must be positive")
+        factors, _ = check_scales(factors)
+        if stride is not None and (isinstance(stride, bool) or stride != int(stride) or int(stride) < 1):
+            raise ValueError(f"stride must be an integer of at least 1 (source pixels), got {stride!r}")
+        if isinstance(max_invalid, bool) or max_invalid != int(max_invalid) or int(max_invalid) < 0:
+            raise ValueError(f"max_invalid must be a non-negative integer, got {max_invalid!r}")
+        parts, keeps = [], []
+        for f in factors:
+            side = f * tile
+            if side * side >= 2 ** 31:
+                raise ValueError(f"factor {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
+            step = side if stride is None else int(stride)
+            for s, y0, x0, h, w in self.split.rectangles:
+                if h < side or w < side:
+                    continue
+                yy, xx = np.meshgrid(y0 + _grid_starts(h, side, step, cover), x0 + _grid_starts(w, side, step, cover), indexing="ij")
+                part = np.empty((yy.size, 4), dtype=np.int32)
+                part[:, 0], part[:, 1], part[:, 2], part[:, 3] = s, yy.reshape(-1), xx.reshape(-1), (f - 1) << 16
+                parts.append(part)
+                if pool.prefix is not None:
+                    P = pool.invalid_prefix(s)
+                    y, x = (torch.from_numpy(part[:, c].astype(np.int64)).to(self.device) for c in (1, 2))
+                    n = P[y + side, x + side].long() - P[y, x + side].long() - P[y + side, x].long() + P[y, x].long()
+                    keeps.append(n <= int(max_invalid) * f * f)
+        rows = np.concatenate(parts) if parts else np.empty((0, 4), dtype=np.int32)
+        if keeps:
+            rows = rows[torch.cat(keeps).cpu().numpy()]                          # the one copy to the host
+        if not len(rows):
+            raise ValueError(f"the grid is empty: no window of tile {tile} at factors {factors} lies inside a held-out rectangle")
+        return WindowList(rows, self.device)
+
+    def gather(self, windows, tile, *, first=0, count=None, out=None):
+        """``ScenePool.gather``: the rows are cut as they are named, whichever half they came from"""
+        return self.pool.gather(windows, tile, first=first, count=count, out=out)
+
+    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, rank=0, world=1):
+        """``GridLoader`` over ``grid(tile, ...)``; rank ``rank`` of ``world`` takes the rows i with ``i % world == rank``, in order"""
+        if not 0 <= int(rank) < int(world):
+            raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
+        full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover)
+        mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
+        return GridLoader(self.pool, mine, batch_size, tile)
 
 
 def _grid_starts(extent, side, step, cover):

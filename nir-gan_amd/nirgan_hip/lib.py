@@ -256,6 +256,13 @@ class SceneGatherDesc(C.Structure):
                 ("n_windows", i64), ("first", i64), ("n", i32), ("rgb", fp), ("nir", fp), ("coords", fp)]
 
 
+SCENE_ORIGIN_COLS = 6                                     # include/nirgan_hip.h: NIRGAN_SCENE_ORIGIN_COLS
+
+
+class SceneOriginsDesc(C.Structure):
+    _fields_ = SceneScaledDesc._fields_ + [("origins", fp), ("origins_host", fp), ("R", i32), ("first", i32 * 8), ("count", i32 * 8)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -320,6 +327,7 @@ PROTOTYPES = {
     "nirgan_scene_sample": (i32, [C.POINTER(SceneSampleDesc), fp]),
     "nirgan_scene_sample_scaled": (i32, [C.POINTER(SceneScaledDesc), fp]),
     "nirgan_scene_gather": (i32, [C.POINTER(SceneGatherDesc), fp]),
+    "nirgan_scene_sample_origins": (i32, [C.POINTER(SceneOriginsDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
