@@ -351,7 +351,9 @@ int nirgan_tap_gather(const nirgan_tap_gather_desc* d, void* stream);
 
 /* Adjoint: dq[b][hh][ww][t] = dz[b][hh-tap_dh[t]][ww-tap_dw[t]], dz = dout*act'(out) inside
  * the crop window and 0 elsewhere; channels t >= ntaps of dq are zeroed; dbias (optional)
- * accumulates sum dz. */
+ * accumulates sum dz (fp32, fixed order); when the float64 sum of the same terms is exactly
+ * 0 (terms of one magnitude and opposite signs: the two halves of a wgangp discriminator
+ * batch) nothing is added. */
 typedef struct {
     const float* dout; const float* out;  /* [B][OH-2crop][OW-2crop] each; out may be NULL when act == NONE */
     int act;

@@ -167,8 +167,14 @@ __global__ void tap_scatter_kernel(const ScatterP p) {
 
 // ONE block of 1024 threads (four elements in flight per thread and trip): the bias gradient of a single-output-channel layer is a sum
 // over its (small) output map; no atomics between blocks, bitwise reproducible.  dbias += the sum.
+// Beside the fp32 sum (fixed order, the value added) the same terms are summed in float64, where every partial sum of fp32 terms of one
+// magnitude is exact: when that sum is exactly 0 -- the +w/n of the fake and the -w/n of the real patches of a wgangp discriminator
+// step, as the two separate sums of the reference's two discriminator calls cancel -- whatever the fp32 order left is rounding residue
+// and nothing is added.  Such a residue is a gradient of pure noise that Adam turns into a step of the last bias, a different one for
+// every way of cutting the batch.
 __global__ __launch_bounds__(1024) void tap_dbias_kernel(const float* __restrict__ dout, const float* __restrict__ out, int act, int64_t n, float* dbias) {
     float s = 0.f;
+    double sd = 0.0;
     for (int64_t i0 = threadIdx.x; i0 < n; i0 += 4096) {
         float g[4];
 #pragma unroll
@@ -181,15 +187,20 @@ __global__ __launch_bounds__(1024) void tap_dbias_kernel(const float* __restrict
             }
         }
         s += (g[0] + g[1]) + (g[2] + g[3]);
+        sd += (double(g[0]) + double(g[1])) + (double(g[2]) + double(g[3]));
     }
     s = ng_wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sd += __shfl_xor(sd, o, 64);
     __shared__ float part[16];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __shared__ double partd[16];
+    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = s; partd[threadIdx.x >> 6] = sd; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float t = 0.f;
-        for (int w = 0; w < 16; ++w) t += part[w];
-        dbias[0] += t;
+        double td = 0.0;
+        for (int w = 0; w < 16; ++w) { t += part[w]; td += partd[w]; }
+        if (td != 0.0) dbias[0] += t;
     }
 }
 

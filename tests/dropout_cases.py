@@ -242,8 +242,10 @@ def eval_mode_is_the_identity(dev, ngf=8, size=32):
     assert drop.dropout_state() == (None, 0), "an eval-mode forward drew a seed or counted a call"
 
 
-def forward64(p, x, n_blocks, masks, embeds=None):
-    """float64 restatement of the generator with the blocks' dropout as a multiplication by the given {0, 2} masks."""
+def forward64(p, x, n_blocks, masks, embeds=None, post_correction=False):
+    """float64 restatement of the generator with the blocks' dropout as a multiplication by the given {0, 2} masks (a net built without
+    dropout carries the blocks' second convolution as conv_block.5: read off the keys).  It runs in the dtype of its arguments."""
+    c2 = "conv_block.6" if "model.10.conv_block.6.weight" in p else "conv_block.5"
     IN = lambda t: F.instance_norm(t, eps=1e-5)                  # noqa: E731
     rp = lambda t, n: F.pad(t, (n,) * 4, mode="reflect")         # noqa: E731
     h = F.relu(IN(F.conv2d(rp(x, 3), p["model.1.weight"], p["model.1.bias"])))
@@ -255,11 +257,12 @@ def forward64(p, x, n_blocks, masks, embeds=None):
         i = 10 + j
         t = F.relu(IN(F.conv2d(rp(h, 1), p[f"model.{i}.conv_block.1.weight"], p[f"model.{i}.conv_block.1.bias"])))
         t = t * masks[j]
-        h = h + IN(F.conv2d(rp(t, 1), p[f"model.{i}.conv_block.6.weight"], p[f"model.{i}.conv_block.6.bias"]))
+        h = h + IN(F.conv2d(rp(t, 1), p[f"model.{i}.{c2}.weight"], p[f"model.{i}.{c2}.bias"]))
     for i in (10 + n_blocks, 13 + n_blocks):
         h = F.relu(IN(F.conv_transpose2d(h, p[f"model.{i}.weight"], p[f"model.{i}.bias"], stride=2, padding=1, output_padding=1)))
     i = 17 + n_blocks
-    return torch.tanh(F.conv2d(rp(h, 3), p[f"model.{i}.weight"], p[f"model.{i}.bias"]))
+    out = torch.tanh(F.conv2d(rp(h, 3), p[f"model.{i}.weight"], p[f"model.{i}.bias"]))
+    return out * p["post_correction_param"] if post_correction else out          # generator_inject.py:133-134
 
 
 def inject_config(ngf, no_dropout=False):

@@ -281,6 +281,16 @@ class _Seq(torch.nn.Module):
         return self.model(x)
 
 
+def stock_patchgan(ndf=8):
+    """the 70 x 70 PatchGAN with instance norm as stock torch.nn (fp32 as built; the reference's state_dict keys)"""
+    nn = torch.nn
+    d = [nn.Conv2d(4, ndf, 4, stride=2, padding=1), nn.LeakyReLU(0.2, True)]
+    for cin, cout, s in ((ndf, 2 * ndf, 2), (2 * ndf, 4 * ndf, 2), (4 * ndf, 8 * ndf, 1)):
+        d += [nn.Conv2d(cin, cout, 4, stride=s, padding=1), nn.InstanceNorm2d(cout), nn.LeakyReLU(0.2, True)]
+    d += [nn.Conv2d(8 * ndf, 1, 4, stride=1, padding=1)]
+    return _Seq(d)
+
+
 def stock_nets(m, ngf=8, n_blocks=6):
     """float64 torch.nn restatement of the two networks (the published pix2pix ResNet generator and 70 x 70 PatchGAN with instance
     norm), built here and filled from the model's state dict"""
@@ -294,11 +304,7 @@ def stock_nets(m, ngf=8, n_blocks=6):
         c = ngf * 2 ** (2 - i)
         g += [nn.ConvTranspose2d(c, c // 2, 3, stride=2, padding=1, output_padding=1), nn.InstanceNorm2d(c // 2), nn.ReLU(True)]
     g += [nn.ReflectionPad2d(3), nn.Conv2d(ngf, 1, 7), nn.Tanh()]
-    d = [nn.Conv2d(4, ngf, 4, stride=2, padding=1), nn.LeakyReLU(0.2, True)]
-    for cin, cout, s in ((ngf, 2 * ngf, 2), (2 * ngf, 4 * ngf, 2), (4 * ngf, 8 * ngf, 1)):
-        d += [nn.Conv2d(cin, cout, 4, stride=s, padding=1), nn.InstanceNorm2d(cout), nn.LeakyReLU(0.2, True)]
-    d += [nn.Conv2d(8 * ngf, 1, 4, stride=1, padding=1)]
-    G, D = _Seq(g).double(), _Seq(d).double()
+    G, D = _Seq(g).double(), stock_patchgan(ngf).double()
     G.load_state_dict({k: v.detach().cpu().double() for k, v in m.netG.state_dict().items()})
     D.load_state_dict({k: v.detach().cpu().double() for k, v in m.netD.state_dict().items()})
     return G, D

@@ -917,6 +917,35 @@ def tap_scatter_against_float64(dev, case):
                 assert dbias.item() == DBIAS0
 
 
+OPPOSITE_HALVES = [(4, 6, 6), (6, 5, 7), (2, 30, 30)]        # the PatchGAN's last map: 2B samples of a [fake ; real] batch, no power of two
+
+
+def tap_scatter_opposite_halves(dev, shape):
+    """dout = +w/n on the first half of the batch and -w/n on the second (a wgangp discriminator step): the bias gradient is a sum of
+    equal and opposite terms and has to leave dbias bitwise where it was -- a residue of the summation order would be a gradient of
+    rounding noise, which Adam turns into a step (step_matrix_cases row w01 found the fused and the Lightning route one step of the
+    last bias apart).  Beside its fp32 sum the library sums the terms in float64, where every partial sum of such terms is exact, and adds
+    nothing when that sum is exactly 0."""
+    B, OH, OW = shape
+    k, qcs = 4, 16
+    qh, qw = OH + k - 1, OW + k - 1
+    a = (torch.tensor(0.37) * (torch.tensor(1.0) / torch.tensor(float(B // 2 * OH * OW)))).item()      # fp32((w) * (1.f / n))
+    dout = torch.full((B, OH, OW), a)
+    dout[B // 2:] = -a
+    dout = dout.to(dev)
+    dq, dbias = nan(B, qh, qw, qcs, dev=dev), torch.full((1,), DBIAS0, device=dev)
+    d = L.TapScatterDesc()
+    d.dout, d.out, d.act = dout.data_ptr(), None, L.ACT_NONE
+    d.B, d.OH, d.OW, d.crop, d.ntaps = B, OH, OW, 0, k * k
+    for t in range(k * k):
+        d.tap_dh[t], d.tap_dw[t] = t // k, t % k
+    d.dq, d.q_hp, d.q_wp, d.q_cs, d.dbias = dq.data_ptr(), qh, qw, qcs, dbias.data_ptr()
+    L.call("nirgan_tap_scatter", C.byref(d), stream(dev))
+    sync(dev)
+    assert dbias.item() == DBIAS0, f"{shape}: dbias moved by {dbias.item() - DBIAS0:.3e}"
+    assert torch.isfinite(dq.cpu()).all()
+
+
 def tap_reference_alone(case):
     for act in (True, False):
         c = tap_case(case, act)

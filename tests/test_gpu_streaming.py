@@ -59,5 +59,10 @@ def test_tap_scatter(case):
     Sc.tap_scatter_against_float64(DEV, case)
 
 
+@pytest.mark.parametrize("shape", Sc.OPPOSITE_HALVES, ids=str)
+def test_tap_scatter_opposite_halves_leave_the_bias_gradient_at_zero(shape):
+    Sc.tap_scatter_opposite_halves(DEV, shape)
+
+
 def test_generator_with_the_unscaled_multiply_injection():
     Sc.unscaled_multiply_generator(DEV)

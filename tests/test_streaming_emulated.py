@@ -75,6 +75,11 @@ def test_tap_scatter(emu, case):
     Sc.tap_scatter_against_float64("cpu", case)
 
 
+@pytest.mark.parametrize("shape", Sc.OPPOSITE_HALVES, ids=str)
+def test_tap_scatter_opposite_halves_leave_the_bias_gradient_at_zero(emu, shape):
+    Sc.tap_scatter_opposite_halves("cpu", shape)
+
+
 def test_generator_with_the_unscaled_multiply_injection(emu):
     Sc.unscaled_multiply_generator("cpu")
     assert {"inject_fwd", "inject_bwd", "bilinear_fwd", "bilinear_bwd"} <= set(emu.calls)
