@@ -1393,6 +1393,88 @@ typedef struct {
 } nirgan_scene_origins_desc;
 int nirgan_scene_sample_origins(const nirgan_scene_origins_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Predicting the NIR band of ONE device-resident scene in place: the scene stays as it is stored (uint16 reflectance or float32,
+ * planar [C][H][W], C >= 3, nothing aligned), the three entries below stand around the generator and nirgan_tile_blend:
+ *   counts   which tiles hold nothing but nodata (they are skipped: the generator never sees them),
+ *   gather   the listed tiles, cut and normalised on the way, plus each tile's lon / lat,
+ *   finish   the blended float scene -> the stored band (uint16 / float16 / float32), nodata pixels marked.
+ * One descriptor serves all three; every entry checks the COMMON fields and its OWN, and reads nothing else.
+ *
+ * Geometry: exactly that of nirgan_tile_count_ov with B = 1.  core = tile - 2*margin, stride = core - overlap, 0 <= overlap <= core/2,
+ * nth / ntw tiles per axis (1 if H <= core, else ceil((H - core)/stride) + 1), nt = nth*ntw tiles numbered t = ti*ntw + tj.  Tile
+ * (ti, tj) reads scene rows ti*stride - margin .. + tile - 1 (columns alike), reflected with period 2*(H-1) as nirgan_tile_gather_ov
+ * reflects; its usable region is rows [ti*stride, ti*stride + core) x columns [tj*stride, tj*stride + core), clipped to the scene:
+ * hy = min(core, H - ti*stride) rows, wx = min(core, W - tj*stride) columns (both >= 1).
+ *
+ * Validity: with has_nodata set, a pixel is INVALID iff any of the planes band[0..2] equals `nodata` there (NIRGAN_SCENE_U16) or is
+ * NaN (NIRGAN_SCENE_F32; `nodata` is not read).  With has_nodata == 0 no pixel is invalid.
+ *
+ * nirgan_scene_tile_invalid   counts[t] = the number of invalid pixels in the clipped usable region of tile t, for all nt tiles.
+ *   One launch, one workgroup per tile (grid-strided), lanes along x; integer sums through a wave reduction and LDS: exact and
+ *   independent of scheduling.  A tile can be skipped iff counts[t] == hy*wx.
+ * nirgan_scene_tile_gather    tiles[k][c][y][x] = (float)scene[band[c]][r(ti*stride - margin + y)][r(tj*stride - margin + x)] / divisor
+ *   for the tile t = ids[k], k = 0 .. n-1: ONE correctly rounded float32 division, so the tile is BITWISE what
+ *   nirgan_tile_gather_ov cuts from the host-converted float scene a[band].astype(float32) / float32(divisor).  Nodata pixels enter as
+ *   nodata / divisor.  ids / ids_host: int32 [n] on the device and the same words in HOST memory; every check reads the host copy:
+ *   strictly ascending, inside 0 .. nt-1.  tile % 4 == 0 and `tiles` 16-byte aligned: a thread stores four pixels at once.
+ *   With geo AND coords set the same launch writes
+ *     coords[k] = { (float)(lon0 + cx*dlon), (float)(lat0 + cy*dlat) },   cx = tj*stride + wx/2 + 0.5,   cy = ti*stride + hy/2 + 0.5
+ *   (integer divisions; then ONE rounded float64 product and ONE rounded float64 sum per axis, not fused, as in nirgan_scene_sample):
+ *   the centre of the tile's clipped usable region.  geo = device { lon0, dlon, lat0, dlat }.  One launch.
+ * nirgan_scene_finish         out[y][x] from v = blended[y][x] and the scene.  An invalid pixel (the rule above, recomputed from the
+ *   three planes) gets nodata_out.  Otherwise
+ *     NIRGAN_SCENE_OUT_U16   t = v * scale (one rounded float32 product); t NaN -> nodata_out; else q = rint(t) (ties to even) clamped to
+ *                            0 .. 65535; q == nodata_out moves to nodata_out + 1, or to 65534 where nodata_out is 65535: a valid
+ *                            pixel is never read as nodata.  nodata_out must be an integer in 0 .. 65535.
+ *     NIRGAN_SCENE_OUT_F16   v rounded to binary16 (nearest even); nodata_out is rounded the same way.
+ *     NIRGAN_SCENE_OUT_F32   v; nodata_out as it is (any float, NaN included).
+ *   One launch; a thread owns four consecutive pixels (vector loads and stores where every address allows, element-wise otherwise).
+ * 64-bit addressing throughout, no atomics, no host synchronisation, every output element has one owner, nothing outside the
+ * outputs is written and they need no initialisation.
+ *
+ * With skipped tiles the nirgan_tile_blend launches no longer cover every tile.  Only invalid pixels can then miss a covering tile (a
+ * pixel inside a skipped tile's usable region is itself invalid), a scene that was zeroed first makes what they hold deterministic,
+ * and the finish overwrites them; every valid pixel sees all of its covering tiles in ascending order as before.
+ *
+ * Argument errors return NIRGAN_ERR_ARG before any launch, the message names the entry.  Common: a null d or scene; unknown dtype;
+ * C < 3; H or W < 1, H*W at 2^31 or more; a band outside 0 .. C-1; has_nodata with a uint16 nodata outside 0 .. 65535; divisor 0 or
+ * NaN; tile < 4 or tile % 4 != 0; margin < 0 or margin >= tile/2; overlap < 0 or past core/2; 2^31 tiles or more.  Counts: null
+ * counts.  Gather: null ids, ids_host or tiles, tiles not 16-byte aligned; n < 1 or n*3*tile*tile at 2^31 or more; an id outside
+ * 0 .. nt-1 or not above its predecessor (the message names the position).  Finish: null blended or out; unknown out_kind;
+ * NIRGAN_SCENE_OUT_U16 with a nodata_out that is not an integer in 0 .. 65535.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_SCENE_OUT_U16 0
+#define NIRGAN_SCENE_OUT_F16 1
+#define NIRGAN_SCENE_OUT_F32 2
+typedef struct {
+    /* common */
+    const void* scene;                    /* device [C][H][W], the first element of plane 0 */
+    int dtype;                            /* NIRGAN_SCENE_U16 or NIRGAN_SCENE_F32 */
+    int C, H, W;
+    int band[3];                          /* the planes of R, G, B */
+    int has_nodata, nodata;               /* nodata: the uint16 value; not read for a float scene */
+    float divisor;
+    int tile, margin, overlap;
+    /* nirgan_scene_tile_invalid */
+    int32_t* counts;                      /* [nt] */
+    /* nirgan_scene_tile_gather */
+    const int32_t* ids;                   /* device [n], strictly ascending tile numbers */
+    const int32_t* ids_host;              /* the same words in HOST memory: every check reads them */
+    int n;
+    float* tiles;                         /* [n][3][tile][tile], 16-byte aligned */
+    const double* geo;                    /* device { lon0, dlon, lat0, dlat }, or NULL */
+    float* coords;                        /* [n][2], or NULL */
+    /* nirgan_scene_finish */
+    const float* blended;                 /* [H][W] */
+    int out_kind;                         /* NIRGAN_SCENE_OUT_* */
+    float scale, nodata_out;
+    void* out;                            /* [H][W] uint16, binary16 or float32 */
+} nirgan_scene_predict_desc;
+int nirgan_scene_tile_invalid(const nirgan_scene_predict_desc* d, void* stream);
+int nirgan_scene_tile_gather(const nirgan_scene_predict_desc* d, void* stream);
+int nirgan_scene_finish(const nirgan_scene_predict_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,23 +13,9 @@
 // later one does acc = fma(w, v, acc).  Whether the lowest-numbered covering tile lies before `first` follows from the geometry
 // alone, which is what selects between starting from the stored value and starting fresh -- the scene needs no initialisation and the
 // result does not depend on how the tiles are split into launches (ascending `first`, one stream).
-#include "common.h"
+#include "tile_dev.h"
 
 namespace {
-
-// ng_reflect continued periodically (period 2 (n - 1)): the same index wherever ng_reflect is defined (one reflection), and an index
-// inside [0, n) for every i -- a tile that is much larger than the scene reads rows more than one reflection away.
-__host__ __device__ __forceinline__ int tb_reflect(int i, int n) {
-    int r = ng_reflect(i, n);
-    if (r < 0 || r >= n) {
-        const int period = 2 * (n - 1);
-        if (period == 0) return 0;
-        r = i % period;
-        if (r < 0) r += period;
-        if (r >= n) r = period - r;
-    }
-    return r;
-}
 
 struct BlendP {
     float* scene; float* tiles;
@@ -153,8 +139,6 @@ inline int blend_grid(int64_t items) {
     const int64_t g = (items + 255) / 256;
     return int(g < 8192 ? (g < 1 ? 1 : g) : 8192);
 }
-
-inline int tiles_per_axis(int extent, int core, int stride) { return extent <= core ? 1 : (extent - core + stride - 1) / stride + 1; }
 
 inline bool tiling_ok(int B, int H, int W, int tile, int margin, int overlap) {
     return B > 0 && H > 0 && W > 0 && tile > 0 && margin >= 0 && 2 * int64_t(margin) < tile && overlap >= 0 && 2 * int64_t(overlap) <= tile - 2 * margin;

@@ -33,6 +33,9 @@ held-out rectangle (widened by ``guard`` pixels), whatever the nodata attempts d
     fit(model, split.train.loader(16, 256, steps_per_epoch=1000, seed=1, scales=(1, 2)),
         split.val.grid_loader(16, 256, factors=(1, 2)), max_epochs=10)
 
+``pool.predict(model, s, ...)`` is the inference side: the NIR band of scene ``s`` through ``nirgan_hip.inference.predict_scene``,
+read in place from the pool's buffer.
+
 Reading ``.tif`` is out of scope (no rasterio here): convert once to ``.npz``.
 """
 from __future__ import annotations
@@ -339,6 +342,25 @@ class ScenePool:
         full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover, scenes=scenes)
         mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
         return GridLoader(self, mine, batch_size, tile)
+
+    def scene(self, s: int) -> torch.Tensor:
+        """Scene ``s`` as a [C, H, W] VIEW of the pool's buffer (int16 bit patterns of a uint16 pool); nothing is copied."""
+        if not 0 <= int(s) < len(self.shapes):
+            raise ValueError(f"scene {s} outside 0 .. {len(self.shapes) - 1}")
+        (h, w), off = self.shapes[int(s)], self.offsets[int(s)]
+        return self.pool[off:off + self.C * h * w].view(self.C, h, w)
+
+    def predict(self, model, s: int, **kw) -> torch.Tensor:
+        """The predicted NIR band [H, W] of scene ``s``: ``nirgan_hip.inference.predict_scene`` on a view of the pool's buffer with
+        the pool's first three ``bands``, its ``divisor``, ``nodata`` and the scene's geotransform row.  ``kw``: the
+        other keywords of ``predict_scene`` (tile, margin, overlap, window, batch, tta, embeds, out, scale, nodata_out)."""
+        from .inference import predict_scene
+        fixed = {"bands", "divisor", "nodata", "geotransform"} & set(kw)
+        if fixed:
+            raise TypeError(f"ScenePool.predict: {sorted(fixed)} come from the pool")
+        view = self.scene(s)
+        return predict_scene(model, view, bands=self.bands[:3], divisor=self.divisor, nodata=self.nodata,
+                             geotransform=None if self.geo is None else self.geo[int(s)], **kw)
 
     def split(self, val, guard=0) -> "PoolSplit":
         """Hold rectangles of the scenes out of training.  ``val``: ``(scene, y0, x0, h, w)`` rectangles in source pixels,

@@ -4,7 +4,9 @@ The reference's create_synthetic_dataset.py (:100-118) runs ``model(hr)`` under 
 then post-processes on the CPU and stores fp16 ``.npz`` files (:49-52, :117).  ``predict_tiled`` adds
 what large scenes need on the GPU side: the scene is cut into tiles that overlap by twice the model's
 reflect padding trick (model/pix2pix.py:91-93,107-108 hides tile-edge artefacts with pad-10 / crop); the
-overlap is discarded, so every output pixel comes from a tile interior.
+overlap is discarded, so every output pixel comes from a tile interior.  ``predict_scene`` is the same flow for ONE scene as it is
+stored (uint16 reflectance or float32, resident on the device): cut and normalised by the gather, tiles of nothing but nodata
+skipped, the blended result written back as uint16 / float16 / float32.
 """
 from __future__ import annotations
 
@@ -217,6 +219,143 @@ def predict_tta(model, x: torch.Tensor, tta: str = "d4", embeds=None) -> torch.T
         return (model(x) if embeds is None else model(x, embeds)).detach()
     run = _ViewsRunner(k, B, C3, H, W, x.device)
     return run(model, x.detach().to(torch.float32).contiguous(), embeds).to(x.dtype)
+
+
+_OUT_DTYPES = {"uint16": torch.int16, "float16": torch.float16, "float32": torch.float32}
+
+
+def _usable_areas(H, W, core, stride, nth, ntw):
+    """pixels of every tile's usable region clipped to the scene, row-major [nth * ntw]"""
+    hy = np.minimum(core, H - np.arange(nth, dtype=np.int64) * stride)
+    wx = np.minimum(core, W - np.arange(ntw, dtype=np.int64) * stride)
+    return (hy[:, None] * wx[None, :]).reshape(-1)
+
+
+@torch.no_grad()
+def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None, geotransform=None, tile: int = 512, margin: int = 16,
+                  overlap=None, window: str = "linear", batch: int = 8, tta: str = "none", embeds=None, out: str = "uint16", scale=None,
+                  nodata_out=None) -> torch.Tensor:
+    """The NIR band of one device-resident scene, predicted in place -> [H, W] device tensor.
+
+    ``scene``: a device tensor [C, H, W], C >= 3, contiguous: uint16 reflectance as the int16 bit patterns ``ScenePool`` stores (or
+    torch.uint16), or float32.  A numpy uint16 / float32 array is uploaded once as it is.  ``bands`` name the planes of R, G, B; every
+    value is divided by ``divisor`` on the way into a tile (one float32 division, as ``a[bands].astype(float32) / float32(divisor)``).
+    ``tile``, ``margin``, ``overlap``, ``window``, ``batch`` and ``tta`` mean what they mean in ``predict_tiled(blend="blend")``;
+    ``overlap=0`` is the plain tiling.
+
+    ``nodata``: a pixel is invalid where any of the three bands equals it (uint16) or is NaN (float32; the value is not used); with
+    None no pixel is.  A tile whose usable region holds only invalid pixels is skipped -- the generator never sees it; no valid pixel
+    changes, since every tile covering a valid pixel still runs on exactly the input it would read otherwise (nodata pixels enter as
+    ``nodata / divisor``).  Which tiles run costs ONE copy of a count per tile to the host, the only synchronisation.
+
+    ``out``: ``"uint16"`` (int16 bit patterns: ``rint(v * scale)`` clamped to 0 .. 65535, ``scale`` defaults to ``divisor``; a valid
+    pixel that lands on ``nodata_out`` moves to the next code), ``"float16"`` (what ``save_nir_npz`` stores) or ``"float32"`` (bitwise
+    ``predict_tiled`` on the converted scene).  Invalid pixels get ``nodata_out``: by default ``nodata`` (0 without) for uint16, NaN for
+    the float kinds.
+
+    ``embeds``: None calls ``model(x)``; a [1, 256] tensor gives every tile that row; ``"coords"`` (needs ``geotransform`` = (lon0,
+    dlon, lat0, dlat), a sequence or a float64 device tensor) has the gather write the lon / lat of every tile's own centre and calls
+    ``model(x, model.satclip_get_inject(coords))``: each tile of a large scene gets the prior of its own location."""
+    import ctypes as C
+    from . import lib as L
+    k = _tta_views(tta, "predict_scene")
+    windows = {"linear": L.BLEND_LINEAR, "cosine": L.BLEND_COSINE}
+    if window not in windows:
+        raise ValueError(f"predict_scene: window must be one of {sorted(windows)}, got {window!r}")
+    if out not in L.SCENE_OUT_KINDS:
+        raise ValueError(f"predict_scene: out must be one of {sorted(L.SCENE_OUT_KINDS)}, got {out!r}")
+    if isinstance(scene, np.ndarray):
+        if scene.dtype not in (np.uint16, np.float32):
+            raise ValueError(f"predict_scene: a numpy scene must be uint16 or float32, got {scene.dtype}")
+        a = np.ascontiguousarray(scene)
+        scene = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to("cpu" if L.is_emulated() else "cuda")
+    if scene.dim() != 3 or scene.dtype not in (torch.int16, torch.uint16, torch.float32) or not scene.is_contiguous():
+        raise ValueError(f"predict_scene: the scene must be a contiguous [C, H, W] tensor of int16 (uint16 bit patterns), uint16 or float32, "
+                         f"got {tuple(scene.shape)} {scene.dtype}")
+    dev = scene.device
+    if dev.type != "cuda" and not L.is_emulated():
+        raise RuntimeError("predict_scene runs on MI355X (cuda tensors) only; there is no CPU path")
+    Cs, H, W = (int(v) for v in scene.shape)
+    is_u16 = scene.dtype != torch.float32
+    bands = tuple(int(b) for b in bands)
+    if Cs < 3 or len(bands) != 3 or any(not 0 <= b < Cs for b in bands):
+        raise ValueError(f"predict_scene: the scene needs at least 3 bands and bands must name three planes in 0 .. C-1, got C {Cs}, bands {bands}")
+    if tile <= 0 or tile % 4 or not 0 <= margin < tile // 2:
+        raise ValueError(f"predict_scene: tile must be a positive multiple of 4 and 0 <= margin < tile // 2 (tile {tile}, margin {margin})")
+    core = tile - 2 * margin
+    overlap = core // 4 if overlap is None else int(overlap)
+    if not 0 <= overlap <= core // 2:
+        raise ValueError(f"predict_scene: overlap {overlap} outside 0 .. core // 2 = {core // 2} (tile {tile}, margin {margin})")
+    if is_u16 and nodata is not None and not 0 <= int(nodata) <= 65535:
+        raise ValueError(f"predict_scene: nodata {nodata} outside 0 .. 65535")
+    kind = L.SCENE_OUT_KINDS[out]
+    if nodata_out is None:
+        nodata_out = (int(nodata) if is_u16 and nodata is not None else 0) if kind == L.SCENE_OUT_U16 else float("nan")
+    be = L.backend()
+    nt = int(be.nirgan_tile_count_ov(1, H, W, tile, margin, overlap))
+    if nt <= 0:
+        raise ValueError(f"predict_scene: bad tiling (scene {H}x{W}, tile {tile}, margin {margin}, overlap {overlap})")
+    stride = core - overlap
+    ntw = 1 if W <= core else -(-(W - core) // stride) + 1
+    st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    geo = None
+    if geotransform is not None:
+        geo = geotransform if torch.is_tensor(geotransform) else torch.tensor([float(v) for v in geotransform], dtype=torch.float64)
+        geo = geo.detach().to(device=dev, dtype=torch.float64).reshape(4).contiguous()
+    if isinstance(embeds, str):
+        if embeds != "coords":
+            raise ValueError(f"predict_scene: embeds must be None, a [1, E] tensor or 'coords', got {embeds!r}")
+        if geo is None:
+            raise ValueError("predict_scene: embeds='coords' needs a geotransform")
+    elif embeds is not None and (embeds.dim() != 2 or embeds.shape[0] != 1):
+        raise ValueError(f"predict_scene: an embeds tensor is one row [1, E] for the whole scene, got {tuple(embeds.shape)}")
+    d = L.ScenePredictDesc()
+    d.scene, d.dtype, d.C, d.H, d.W = scene.data_ptr(), L.SCENE_U16 if is_u16 else L.SCENE_F32, Cs, H, W
+    d.band = (C.c_int * 3)(*bands)
+    d.has_nodata, d.nodata = int(nodata is not None), int(nodata) if is_u16 and nodata is not None else 0
+    d.divisor, d.tile, d.margin, d.overlap = float(divisor), tile, margin, overlap
+    if nodata is not None:
+        counts = torch.empty(nt, dtype=torch.int32, device=dev)
+        d.counts = counts.data_ptr()
+        L.check(be.nirgan_scene_tile_invalid(C.byref(d), st), "scene_tile_invalid")
+        full = counts.cpu().numpy().astype(np.int64) >= _usable_areas(H, W, core, stride, nt // ntw, ntw)     # the one copy to the host
+        ids_host = np.ascontiguousarray(np.flatnonzero(~full).astype(np.int32))
+    else:
+        ids_host = np.arange(nt, dtype=np.int32)
+    ids = torch.from_numpy(ids_host.copy()).to(dev)
+    total = len(ids_host)
+    acc = torch.zeros(1, 1, H, W, dtype=torch.float32, device=dev)
+    step = max(1, batch // k)
+    if total:
+        tiles = torch.empty(min(step, total), 3, tile, tile, dtype=torch.float32, device=dev)
+        coords = torch.empty(min(step, total), 2, dtype=torch.float32, device=dev) if isinstance(embeds, str) else None
+        run = _ViewsRunner(k, min(step, total), 3, tile, tile, dev) if k > 1 else None
+        b = L.TileBlendDesc()
+        b.B, b.C, b.H, b.W, b.tile, b.margin, b.overlap, b.window = 1, 1, H, W, tile, margin, overlap, windows[window]
+        b.scene = acc.data_ptr()
+        d.tiles, d.geo, d.coords = tiles.data_ptr(), None if coords is None else geo.data_ptr(), None if coords is None else coords.data_ptr()
+    for i0 in range(0, total, step):
+        n = min(step, total - i0)
+        d.ids, d.ids_host, d.n = ids.data_ptr() + 4 * i0, ids_host.ctypes.data + 4 * i0, n
+        L.check(be.nirgan_scene_tile_gather(C.byref(d), st), "scene_tile_gather")
+        x = tiles[:n]
+        e = None if embeds is None else (model.satclip_get_inject(coords[:n]) if coords is not None else embeds.expand(n, -1))
+        if run is not None:
+            pred = run(model, x, e)
+        else:
+            pred = (model(x) if e is None else model(x, e)).detach().to(torch.float32).contiguous()
+            if pred.shape != (n, 1, tile, tile):
+                raise ValueError(f"predict_scene needs a model that maps n x 3 x T x T to n x 1 x T x T, got {tuple(pred.shape)}")
+        chunk = ids_host[i0:i0 + n]
+        starts = np.concatenate(([0], np.flatnonzero(np.diff(chunk) != 1) + 1, [n]))          # maximal runs of consecutive tile numbers
+        for a0, a1 in zip(starts[:-1], starts[1:]):
+            b.first, b.n, b.tiles = int(chunk[a0]), int(a1 - a0), pred.data_ptr() + 4 * int(a0) * tile * tile
+            L.check(be.nirgan_tile_blend(C.byref(b), st), "tile_blend")
+    res = torch.empty(H, W, dtype=_OUT_DTYPES[out], device=dev)
+    d.blended, d.out_kind, d.out = acc.data_ptr(), kind, res.data_ptr()
+    d.scale, d.nodata_out = float(divisor if scale is None else scale), float(nodata_out)
+    L.check(be.nirgan_scene_finish(C.byref(d), st), "scene_finish")
+    return res
 
 
 def save_nir_npz(pred_nir: torch.Tensor, out_path: str, name: str) -> str:

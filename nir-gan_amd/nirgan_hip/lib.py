@@ -263,6 +263,17 @@ class SceneOriginsDesc(C.Structure):
     _fields_ = SceneScaledDesc._fields_ + [("origins", fp), ("origins_host", fp), ("R", i32), ("first", i32 * 8), ("count", i32 * 8)]
 
 
+SCENE_OUT_U16, SCENE_OUT_F16, SCENE_OUT_F32 = 0, 1, 2     # include/nirgan_hip.h: NIRGAN_SCENE_OUT_*
+SCENE_OUT_KINDS = {"uint16": SCENE_OUT_U16, "float16": SCENE_OUT_F16, "float32": SCENE_OUT_F32}
+
+
+class ScenePredictDesc(C.Structure):
+    _fields_ = [("scene", fp), ("dtype", i32), ("C", i32), ("H", i32), ("W", i32), ("band", i32 * 3), ("has_nodata", i32), ("nodata", i32),
+                ("divisor", f32), ("tile", i32), ("margin", i32), ("overlap", i32), ("counts", fp),
+                ("ids", fp), ("ids_host", fp), ("n", i32), ("tiles", fp), ("geo", fp), ("coords", fp),
+                ("blended", fp), ("out_kind", i32), ("scale", f32), ("nodata_out", f32), ("out", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -328,6 +339,9 @@ PROTOTYPES = {
     "nirgan_scene_sample_scaled": (i32, [C.POINTER(SceneScaledDesc), fp]),
     "nirgan_scene_gather": (i32, [C.POINTER(SceneGatherDesc), fp]),
     "nirgan_scene_sample_origins": (i32, [C.POINTER(SceneOriginsDesc), fp]),
+    "nirgan_scene_tile_invalid": (i32, [C.POINTER(ScenePredictDesc), fp]),
+    "nirgan_scene_tile_gather": (i32, [C.POINTER(ScenePredictDesc), fp]),
+    "nirgan_scene_finish": (i32, [C.POINTER(ScenePredictDesc), fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
