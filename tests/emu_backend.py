@@ -7,6 +7,7 @@ plumbing, plan ordering, flat parameters, trainer, data parallel reducer) can be
 against the oracle WITHOUT a GPU.  It is never used by the product path, smoke() or bench.py.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -425,47 +426,88 @@ class EmuBackend:
             blocks += int(N) * ((int(K) + 1023) // 1024)
         return 0 if blocks == total_blocks else self._fail("pack_rows_batch: total_blocks mismatch")
 
-    # ------------------------------------------------------------------ SatCLIP location encoder
+    # ------------------------------------------------------------------ SatCLIP location encoder (csrc/locenc.hip)
+    # The kernel's steps as methods of their own, so that tests/test_locenc_emulated.py can plant one error in one of them.
+    LOCENC_MAX_LAYERS, LOCENC_MAX_WIDTH = 8, 2048
+
+    def _locenc_cos_theta(self, theta):
+        """libm's cos, one element at a time: a row's bits do not depend on the batch it is evaluated in"""
+        return np.array([math.cos(t) for t in theta])
+
+    def _locenc_decode(self, f):
+        """feature index -> (l, m)"""
+        l = math.isqrt(f)
+        return l, f - l * l - l
+
+    def _locenc_step(self, q, am, x, pmmp1, pmm):
+        return ((2.0 * q - 1.0) * x * pmmp1 - (q + am - 1.0) * pmm) / (q - am)
+
+    def _locenc_legendre(self, l, am, x):
+        pmm = np.ones_like(x)
+        if am > 0:
+            somx2, fact = np.sqrt((1 - x) * (1 + x)), 1.0
+            for _ in range(am):
+                pmm = pmm * (-fact) * somx2
+                fact += 2.0
+        if l == am:
+            return pmm
+        pmmp1 = x * (2.0 * am + 1.0) * pmm
+        if l == am + 1:
+            return pmmp1
+        P = np.zeros_like(x)
+        for q in range(am + 2, l + 1):
+            P = self._locenc_step(q, am, x, pmmp1, pmm)
+            pmm, pmmp1 = pmmp1, P
+        return P
+
+    def _locenc_azimuth(self, m, phi):
+        """cos(m phi) for m > 0, sin(|m| phi) for m < 0 (libm, one element at a time)"""
+        return np.array([math.cos(m * p) if m > 0 else math.sin(-m * p) for p in phi])
+
+    def _locenc_harmonics(self, x, phi, K, L_):
+        Y = np.zeros((x.size, L_ * L_))
+        for f in range(L_ * L_):
+            l, m = self._locenc_decode(f)
+            P = self._locenc_legendre(l, abs(m), x)
+            Y[:, f] = K[f] * P if m == 0 else K[f] * self._locenc_azimuth(m, phi) * P
+        return Y
+
+    def _locenc_layer(self, h, W, b, w0, i):
+        """layer i of the table: [B][din] -> [B][dout], one coordinate at a time like the kernel's one workgroup per coordinate"""
+        h = np.stack([W @ row for row in h])
+        if b is not None:
+            h = h + b
+        return np.sin(w0[i] * h) if w0[i] != 0.0 else h
+
     def nirgan_location_encoder(self, ref, stream=None):
-        d = obj(ref)
+        d = obj(ref) if ref is not None else None
         self.calls.append("locenc")
+        if d is None or not (d.lonlat and d.sh_norm and d.weights and d.biases and d.dims and d.w0 and d.out):
+            return self._fail("location_encoder: null pointer")
+        if d.B <= 0:
+            return self._fail("location_encoder: empty batch")
+        if d.L < 1 or d.L * d.L > self.LOCENC_MAX_WIDTH:
+            return self._fail(f"location_encoder: legendre_polys={d.L} out of range (L*L <= {self.LOCENC_MAX_WIDTH})")
+        if d.nlayers < 1 or d.nlayers > self.LOCENC_MAX_LAYERS:
+            return self._fail(f"location_encoder: {d.nlayers} linear layers (1..{self.LOCENC_MAX_LAYERS})")
         nf = d.L * d.L
-        if d.dims[0] != nf or d.nlayers < 1 or d.nlayers > 8:
-            return self._fail("location_encoder: bad layer table")
+        if d.dims[0] != nf:
+            return self._fail(f"location_encoder: first layer expects {d.dims[0]} inputs, the harmonics give {nf}")
+        for i in range(d.nlayers):
+            if not d.weights[i]:
+                return self._fail(f"location_encoder: layer {i} has no weight")
+            if not (1 <= d.dims[i] <= self.LOCENC_MAX_WIDTH and 1 <= d.dims[i + 1] <= self.LOCENC_MAX_WIDTH):
+                return self._fail(f"location_encoder: layer {i} is {d.dims[i]} -> {d.dims[i + 1]} (width <= {self.LOCENC_MAX_WIDTH})")
         ll = arr(d.lonlat, d.B * 2, np.float64).reshape(d.B, 2)
         K = arr(d.sh_norm, nf, np.float64)
         phi, theta = np.deg2rad(ll[:, 0] + 180.0), np.deg2rad(ll[:, 1] + 90.0)
-        x = np.cos(theta)
-        Y = np.zeros((d.B, nf))
-        for l in range(d.L):
-            for m in range(-l, l + 1):
-                am = abs(m)
-                pmm = np.ones_like(x)
-                if am > 0:
-                    somx2, fact = np.sqrt((1 - x) * (1 + x)), 1.0
-                    for _ in range(am):
-                        pmm = pmm * (-fact) * somx2
-                        fact += 2.0
-                if l == am:
-                    P = pmm
-                else:
-                    pmmp1 = x * (2.0 * am + 1.0) * pmm
-                    P = pmmp1
-                    for q in range(am + 2, l + 1):
-                        P = ((2.0 * q - 1.0) * x * pmmp1 - (q + am - 1.0) * pmm) / (q - am)
-                        pmm, pmmp1 = pmmp1, P
-                f = l * l + l + m
-                Y[:, f] = K[f] * P if m == 0 else (K[f] * np.cos(m * phi) * P if m > 0 else K[f] * np.sin(am * phi) * P)
+        Y = self._locenc_harmonics(self._locenc_cos_theta(theta), phi, K, d.L)
         if d.features:
             arr(d.features, d.B * nf, np.float64)[:] = Y.reshape(-1)
-        h = Y
+        h, w0 = Y, [d.w0[i] for i in range(d.nlayers)]
         for i in range(d.nlayers):
             W = arr(d.weights[i], d.dims[i + 1] * d.dims[i], np.float64).reshape(d.dims[i + 1], d.dims[i])
-            h = h @ W.T
-            if d.biases[i]:
-                h = h + arr(d.biases[i], d.dims[i + 1], np.float64)
-            if d.w0[i] != 0.0:
-                h = np.sin(d.w0[i] * h)
+            h = self._locenc_layer(h, W, arr(d.biases[i], d.dims[i + 1], np.float64) if d.biases[i] else None, w0, i)
         arr(d.out, d.B * d.dims[d.nlayers], np.float64)[:] = h.reshape(-1)
         return 0
 
