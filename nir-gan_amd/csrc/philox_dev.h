@@ -1,5 +1,5 @@
 // Philox4x32-10 (include/nirgan_hip.h: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), shared by the
-// counter-based generators of the library: the dropout mask (dropout.hip) and the scene sampler (scenepool.hip).
+// counter-based generators of the library: the dropout mask (dropout.hip) and the scene sampler (scenesample.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

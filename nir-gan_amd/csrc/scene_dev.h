@@ -1,6 +1,7 @@
-// Pieces the scene entries share (scenepool.hip: nirgan_scene_sample; scenescale.hip: nirgan_scene_sample_scaled, nirgan_scene_gather,
-// nirgan_scene_sample_origins): the padded 64 x 64 LDS block of the gathers, one attempt of the draw on the words of one Philox call
-// (over whole scenes: sp_attempt; over a table of origin rectangles: so_attempt), and the coords' unfused product and sum.
+// Device pieces and table checks of the scene entries (scenesample.hip: nirgan_scene_sample, nirgan_scene_sample_scaled,
+// nirgan_scene_gather, nirgan_scene_sample_origins; scenepredict.hip takes the unfused product and sum): the padded 64 x 64 LDS block
+// of the gather, the prefix count of a window, one attempt of the draw on the words of one Philox call (over whole scenes: sp_attempt;
+// over a table of origin rectangles: so_attempt; each is its own index -> (s, y0, x0) step), and the coords.
 #pragma once
 #include "common.h"
 #include "philox_dev.h"
@@ -16,6 +17,15 @@ __device__ __forceinline__ double sp_mul_then_add(double a, double x, double y) 
 #pragma clang fp contract(off)
     const double m = x * y;
     return a + m;
+}
+
+// the number of invalid pixels in the T x T window at (y0, x0) of the scene with table row `scene`; 0 where the scene has no prefix
+// table or prefix is null (the row is then not read: a draw without tables waits for one load less)
+__device__ __forceinline__ int64_t sp_invalid(const int32_t* __restrict__ prefix, const int64_t* __restrict__ scene, int y0, int x0, int T) {
+    if (!prefix || scene[4] < 0) return 0;
+    const int32_t* __restrict__ P = prefix + scene[4];
+    const int64_t ld = scene[2] + 1;
+    return int64_t(P[(y0 + T) * ld + x0 + T]) - P[y0 * ld + x0 + T] - P[(y0 + T) * ld + x0] + P[y0 * ld + x0];
 }
 
 // One attempt: the window that the words w name among the `total` windows of side T of table [S][TC], and the number of invalid
@@ -36,13 +46,7 @@ __device__ __forceinline__ int64_t sp_attempt(const uint32_t w[4], const int64_t
     y0 = int(r / nx);
     x0 = int(r % nx);
     view = int(w[2] & uint32_t(views - 1));
-    int64_t n = 0;
-    if (prefix && row[4] >= 0) {
-        const int32_t* __restrict__ P = prefix + row[4];
-        const int64_t ld = W + 1;
-        n = int64_t(P[(y0 + T) * ld + x0 + T]) - P[y0 * ld + x0 + T] - P[(y0 + T) * ld + x0] + P[y0 * ld + x0];
-    }
-    return n;
+    return sp_invalid(prefix, row, y0, x0, T);
 }
 
 constexpr int OC = NIRGAN_SCENE_ORIGIN_COLS;
@@ -66,14 +70,7 @@ __device__ __forceinline__ int64_t so_attempt(const uint32_t w[4], const int64_t
     y0 = int(row[1] + r / ow);
     x0 = int(row[2] + r % ow);
     view = int(w[2] & uint32_t(views - 1));
-    const int64_t* __restrict__ scene = table + int64_t(s) * TC;
-    int64_t n = 0;
-    if (prefix && scene[4] >= 0) {
-        const int32_t* __restrict__ P = prefix + scene[4];
-        const int64_t ld = scene[2] + 1;
-        n = int64_t(P[(y0 + T) * ld + x0 + T]) - P[y0 * ld + x0 + T] - P[(y0 + T) * ld + x0] + P[y0 * ld + x0];
-    }
-    return n;
+    return sp_invalid(prefix, table + int64_t(s) * TC, y0, x0, T);
 }
 
 // coords[b] of a window of side T at (y0, x0) of a scene with geotransform g = (lon0, dlon, lat0, dlat)
@@ -83,12 +80,22 @@ __device__ __forceinline__ void sp_centre(const double* __restrict__ g, int y0, 
     out[1] = float(sp_mul_then_add(g[2], cy, g[3]));
 }
 
+// the extents of scenes s0 .. s1-1 of a [S][TC] host table: sp_check_table asks scene by scene, between its other checks; an entry
+// that reads no cum_windows asks for all S at once
+static inline int sp_check_sides(const char* who, const int64_t* table_host, int s0, int s1) {
+    for (int s = s0; s < s1; ++s) {
+        const int64_t* r = table_host + int64_t(s) * TC;
+        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
+    }
+    return NIRGAN_OK;
+}
+
 // the argument checks of one [S][TC] host table for windows of side T; on success *total_out = cum_windows[S-1] (which may be 0)
 static inline int sp_check_table(const char* who, const int64_t* table_host, int S, int64_t T, int64_t* total_out) {
     int64_t total = 0;
     for (int s = 0; s < S; ++s) {
         const int64_t* r = table_host + int64_t(s) * TC;
-        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
+        if (int e = sp_check_sides(who, table_host, s, s + 1)) return e;
         if (r[1] >= T && r[2] >= T) total += (r[1] - T + 1) * (r[2] - T + 1);   // each term below 2^62: the sum cannot wrap before the bound
         NG_REQUIRE(total < (int64_t(1) << 62), "%s: the pool has 2^62 windows or more", who);
         NG_REQUIRE(r[3] == total, "%s: cum_windows of scene %d is not the running window count for tile %lld", who, s, (long long)T);

@@ -1,10 +1,16 @@
-// Multi-scale training batches from device-resident scenes: nirgan_scene_sample_scaled; and the same gather on a list
-// of windows the caller names: nirgan_scene_gather; and the draw from a table of rectangles of window origins with the
-// same gather behind it: nirgan_scene_sample_origins, at the end of the file.
+// Batches drawn and cut from device-resident scenes, four entries on one draw and one gather:
+//   nirgan_scene_sample            the draw over whole scenes with the one factor 1;
+//   nirgan_scene_sample_scaled     the draw over whole scenes, one table per factor;
+//   nirgan_scene_gather            no draw: the gather on a list of windows the caller names;
+//   nirgan_scene_sample_origins    the draw over a table of rectangles of window origins.
 //
-// The draw of scenepool.hip with one more decision: sample b takes its resolution factor f from the fourth Philox word of attempt 0,
-// cuts a window of side L = f * T and delivers the T x T tile of the means of its f x f blocks.  Two launches, as there:
-//   draw    one thread per sample; the attempts run on the table of the drawn scale and accept n <= max_invalid * f * f;
+// The pool keeps the scenes as they are stored (uint16 or float, planar, nothing aligned).  Sample b takes its resolution factor f
+// from the fourth Philox word of attempt 0, cuts a window of side L = f * T and delivers the T x T tile of the means of its f x f
+// blocks.  Two launches:
+//   draw    one thread per sample: Philox4x32-10 on (seed; draw, sample0 + b, attempt) -> an index among all windows of the drawn
+//           scale (the high word of a 64 x 64 bit product: no modulo bias beyond 2^-64 * total), which the SOURCE of the draw turns
+//           into (scene, y0, x0) -- a binary search of running counts either way, sp_attempt / so_attempt of scene_dev.h -- then the
+//           rejection test n <= max_invalid * f * f on four entries of the scene's invalid-prefix table, the view, the coords;
 //   gather  one 256-thread block per 64 x 64 block of D, the T x T mean image of one plane BEFORE the view, grid-strided.  A wave owns
 //           D row p (16 rows per wave and block).  It reads the f source rows p*f .. p*f + f-1 with the lanes ALONG the source row:
 //           f chunks of 64 consecutive elements per row, one element per lane, every source element fetched once.  The loads are
@@ -21,7 +27,8 @@
 //           e * LDQ mod 32 = e * ceil(32 / f) tile the 32 banks: free of conflicts for f = 2, 4, 8, at most 2-way for the others,
 //           which costs a dword store nothing.  A strip belongs to ONE wave, so a wave-level barrier orders it, not __syncthreads.
 //           Plain views (0 .. 3) store from the registers, lane q -> output column q or T-1-q: 256 contiguous bytes per wave either
-//           way.  Transposing views (4 .. 7) turn the block in the 64 x 65 padded LDS block of scenepool.hip.
+//           way.  Transposing views (4 .. 7) turn the block in LDS with rows padded to 65 floats, as tileviews.hip does (written
+//           with stride 65, read with stride 1: no bank conflict).
 //           f is uniform per block (one sample per block) and selects a template instance: the f x f loops unroll, nothing is
 //           indexed dynamically, no scratch.  The kernel comes in two widths, factors to 4 and factors to 8, picked by the call's
 //           largest factor.  Every output element has one owner, stores are one dword per lane, no atomics.
@@ -38,43 +45,71 @@ constexpr int STRIP = MAXF * strip_ld(MAXF);                                    
 static_assert(2 * strip_ld(2) <= STRIP && 3 * strip_ld(3) <= STRIP && 4 * strip_ld(4) <= STRIP && 5 * strip_ld(5) <= STRIP &&
               6 * strip_ld(6) <= STRIP && 7 * strip_ld(7) <= STRIP, "strip too small");
 
-struct ScaledP {
-    const void* pool;
+// A source of the draw names what it draws from at scale k (`scale`, asked with a constant k only: the scale differs from lane to
+// lane) and turns the words of one attempt there into a window of side L and its invalid count.
+struct Scenes {                          // every window of every scene: one table per scale
     const int64_t* table;                // [K][S][TC]
-    const int32_t* prefix;
-    const double* geo;
-    int64_t total[MAXK];                 // windows of the whole pool at scale k
-    int64_t band[4];
-    int factor[MAXK];
-    uint32_t cumw[MAXK], wtot;           // running weights; cumw[K-1] = wtot < 2^32
-    int K, S, T, B, views, max_invalid, nb;
-    int64_t nblk;                        // B * 4 * nb * nb
-    float divisor;
-    uint32_t seed_lo, seed_hi, draw_lo, draw_hi, sample0;
-    float* rgb; float* nir; float* coords;
-    int32_t* window;                     // written by the draw
-    const int32_t* rows;                 // read by the gather: the draw's window, or the caller's list (nirgan_scene_gather)
+    int S;
+    struct Scale { const int64_t* table; };
+    __device__ __forceinline__ Scale scale(int k) const { return {table + int64_t(k) * S * TC}; }
+    __device__ __forceinline__ int64_t attempt(const uint32_t w[4], const Scale& at, const int32_t* __restrict__ prefix, int L, int64_t total,
+                                               int views, int& s, int& y0, int& x0, int& view) const {
+        return sp_attempt(w, at.table, prefix, S, L, total, views, s, y0, x0, view);
+    }
+};
+struct Origins {                         // the windows whose origins the rows list: scale k owns rows first[k] .. first[k] + count[k] - 1
+    int first[MAXK], count[MAXK];
+    const int64_t* table;                // [S][TC]: W_s and the prefix offset are read
+    const int64_t* origins;              // [R][OC]
+    struct Scale { const int64_t* rows; int count; };
+    __device__ __forceinline__ Scale scale(int k) const { return {origins + int64_t(first[k]) * OC, count[k]}; }
+    __device__ __forceinline__ int64_t attempt(const uint32_t w[4], const Scale& at, const int32_t* __restrict__ prefix, int L, int64_t total,
+                                               int views, int& s, int& y0, int& x0, int& view) const {
+        return so_attempt(w, table, at.rows, at.count, prefix, L, total, views, s, y0, x0, view);
+    }
 };
 
-__global__ __launch_bounds__(256) void scene_scaled_draw_kernel(const ScaledP p) {
+// The draw, whatever its windows are drawn from.
+struct DrawCommon {
+    const int32_t* prefix;
+    const double* geo;
+    int64_t total[MAXK];                 // windows of scale k
+    int factor[MAXK];
+    uint32_t cumw[MAXK], wtot;           // running weights; cumw[K-1] = wtot < 2^32
+    int K, T, B, views, max_invalid;
+    uint32_t seed_lo, seed_hi, draw_lo, draw_hi, sample0;
+    float* coords;
+    int32_t* window;
+};
+
+// The draw's one argument: the common block and the source's few fields.  The kernel is ONE wave that waits for every 64-byte line
+// of its arguments that it reads with scalar loads, so the order of the two is not free, and it is the measured one for each source
+// (DESIGN 3.13): with the common block in front, nirgan_scene_sample_origins took 0.26 us more per call than with it behind
+// (22.18 against 21.92 us); with it behind, nirgan_scene_sample_scaled took 0.2 us more than with it in front.
+template <typename Source> struct DrawP;
+template <> struct DrawP<Scenes> : DrawCommon, Scenes {};
+template <> struct DrawP<Origins> : Origins, DrawCommon {};
+
+template <typename Source>
+__global__ __launch_bounds__(256) void scene_draw_kernel(const DrawP<Source> p) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
     uint32_t w[4];
     philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), 0u, p.seed_lo, p.seed_hi, w);
     const uint32_t pick = uint32_t((uint64_t(w[3]) * uint64_t(p.wtot)) >> 32);             // floor(w3 * Wtot / 2^32) < Wtot
-    int k = 0, f = p.factor[0];
+    int f = p.factor[0];
     int64_t total = p.total[0];
+    typename Source::Scale at = p.scale(0);
 #pragma unroll
     for (int j = 1; j < MAXK; ++j)       // cumw rises: the last j with cumw[j-1] <= pick is the first with cumw[j] > pick
-        if (j < p.K && p.cumw[j - 1] <= pick) { k = j; f = p.factor[j]; total = p.total[j]; }
+        if (j < p.K && p.cumw[j - 1] <= pick) { f = p.factor[j]; total = p.total[j]; at = p.scale(j); }
     const int L = f * p.T;
-    const int64_t* __restrict__ table = p.table + int64_t(k) * p.S * TC;
     const int64_t most = int64_t(p.max_invalid) * f * f;
     int s = 0, y0 = 0, x0 = 0, view = 0, a = 0;
     bool ok = false;
     for (; a < NIRGAN_SCENE_ATTEMPTS; ++a) {
         if (a > 0) philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), uint32_t(a), p.seed_lo, p.seed_hi, w);
-        const int64_t n = sp_attempt(w, table, p.prefix, p.S, L, total, p.views, s, y0, x0, view);
+        const int64_t n = p.attempt(w, at, p.prefix, L, total, p.views, s, y0, x0, view);
         if (n <= most) { ok = true; break; }
     }
     if (!ok) a = NIRGAN_SCENE_ATTEMPTS - 1;
@@ -83,6 +118,19 @@ __global__ __launch_bounds__(256) void scene_scaled_draw_kernel(const ScaledP p)
     o[3] = int32_t(uint32_t(view) | (uint32_t(a) << 8) | (uint32_t(f - 1) << 16) | (ok ? 0u : 0x80000000u));
     if (p.geo && p.coords) sp_centre(p.geo + int64_t(s) * 4, y0, x0, L, p.coords + int64_t(b) * 2);
 }
+
+// The gather: the rows it cuts and what it cuts them from.
+struct GatherP {
+    const void* pool;
+    const int64_t* table;                // [K][S][TC]; with K = 1 the one table serves every row, whatever its factor
+    int64_t band[4];                     // selected plane numbers
+    int factor[MAXK];                    // of table k (not read with K = 1)
+    int K, S, T, nb;                     // nb: blocks per tile side
+    int64_t nblk;                        // rows * 4 * nb * nb
+    float divisor;
+    float* rgb; float* nir;
+    const int32_t* rows;                 // the draw's window, or the caller's list (nirgan_scene_gather)
+};
 
 // orders the LDS traffic of ONE wave: what its lanes stored before is what its lanes load after
 __device__ __forceinline__ void wave_sync() {
@@ -182,7 +230,7 @@ __device__ __forceinline__ void gather_block(const T* __restrict__ src, int64_t 
 // FMAX: the largest factor this instance holds code for (4 or 8).  The registers of a kernel are those of its widest case, so a call
 // whose factors stop at 4 -- the usual one -- runs the instance that stops there, at 4 waves per SIMD instead of 3.
 template <typename T, int FMAX>
-__global__ __launch_bounds__(256) void scene_scaled_gather_kernel(const ScaledP p) {
+__global__ __launch_bounds__(256) void scene_scaled_gather_kernel(const GatherP p) {
     __shared__ float tile[SP_B * SP_LD];
     __shared__ int strips[4 * STRIP];
     const T* __restrict__ pool = static_cast<const T*>(p.pool);
@@ -225,7 +273,7 @@ __global__ __launch_bounds__(256) void scene_scaled_gather_kernel(const ScaledP 
 }
 
 // fmax: the largest factor among the rows the launch reads
-void launch_gather(const ScaledP& p, int dtype, int fmax, hipStream_t st) {
+void launch_gather(const GatherP& p, int dtype, int fmax, hipStream_t st) {
     const int grid = int(p.nblk < 16384 ? p.nblk : 16384);
     const bool wide = fmax > 4;
     const dim3 g(grid), t(256);
@@ -238,61 +286,7 @@ void launch_gather(const ScaledP& p, int dtype, int fmax, hipStream_t st) {
     }
 }
 
-}  // namespace
-
-extern "C" int nirgan_scene_sample_scaled(const nirgan_scene_scaled_desc* d, void* stream) {
-    static const char* who = "scene_sample_scaled";
-    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->rgb && d->nir && d->window, "%s: null pointer", who);
-    NG_REQUIRE(d->dtype == NIRGAN_SCENE_U16 || d->dtype == NIRGAN_SCENE_F32, "%s: unknown dtype %d", who, d->dtype);
-    NG_REQUIRE(d->S > 0 && d->C >= 4, "%s: bad pool (S %d, C %d; C must be at least 4)", who, d->S, d->C);
-    NG_REQUIRE(d->views == 1 || d->views == 4 || d->views == 8, "%s: views %d is not 1, 4 or 8", who, d->views);
-    for (int k = 0; k < 4; ++k) NG_REQUIRE(d->band[k] >= 0 && d->band[k] < d->C, "%s: band %d outside 0 .. C-1", who, d->band[k]);
-    const int64_t T = d->tile;
-    NG_REQUIRE(d->B > 0 && T > 0 && T * T < LIM31 && T * T * d->B < LIM31, "%s: B, tile or B*tile*tile is not in 1 .. 2^31-1 (B %d, tile %d)", who, d->B, d->tile);
-    NG_REQUIRE(d->divisor == d->divisor && d->divisor != 0.0f, "%s: divisor is 0 or NaN", who);
-    NG_REQUIRE(d->max_invalid >= 0, "%s: negative max_invalid", who);
-    NG_REQUIRE(d->pool_elems >= 0 && d->prefix_elems >= 0, "%s: negative pool_elems or prefix_elems", who);
-    NG_REQUIRE(d->K >= 1 && d->K <= MAXK, "%s: K %d outside 1 .. %d", who, d->K, MAXK);
-    ScaledP p;
-    uint64_t wtot = 0;
-    for (int k = 0; k < d->K; ++k) {
-        const int f = d->factor[k];
-        NG_REQUIRE(f >= 1 && f <= MAXF, "%s: factor %d outside 1 .. %d", who, f, MAXF);
-        NG_REQUIRE(k == 0 || f > d->factor[k - 1], "%s: the factors are not strictly increasing (%d after %d)", who, f, d->factor[k - 1]);
-        NG_REQUIRE(d->weight[k] > 0, "%s: the weight of factor %d is 0", who, f);
-        wtot += d->weight[k];
-        NG_REQUIRE(wtot < (uint64_t(1) << 32), "%s: the weights sum to 2^32 or more", who);
-        NG_REQUIRE(f * T * f * T < LIM31, "%s: the window of factor %d, (factor*tile)^2, is 2^31 or more", who, f);
-        p.factor[k] = f;
-        p.cumw[k] = uint32_t(wtot);
-    }
-    for (int k = 0; k < d->K; ++k) {
-        const int64_t* th = d->table_host + int64_t(k) * d->S * TC;
-        if (int e = sp_check_table(who, th, d->S, p.factor[k] * T, &p.total[k])) return e;
-        NG_REQUIRE(p.total[k] > 0, "%s: no scene holds a window of factor %d (side %lld)", who, p.factor[k], (long long)(p.factor[k] * T));
-        if (int e = sp_check_extents(who, th, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
-    }
-    p.wtot = uint32_t(wtot);
-    for (int k = d->K; k < MAXK; ++k) { p.factor[k] = 0; p.cumw[k] = 0; p.total[k] = 0; }
-    p.pool = d->pool; p.table = d->table; p.prefix = d->prefix; p.geo = d->geo;
-    for (int k = 0; k < 4; ++k) p.band[k] = d->band[k];
-    p.K = d->K; p.S = d->S; p.T = d->tile; p.B = d->B; p.views = d->views; p.max_invalid = d->max_invalid;
-    p.nb = (d->tile + SP_B - 1) / SP_B;
-    p.nblk = int64_t(d->B) * 4 * p.nb * p.nb;
-    p.divisor = d->divisor;
-    p.seed_lo = d->seed_lo; p.seed_hi = d->seed_hi; p.draw_lo = uint32_t(d->draw); p.draw_hi = uint32_t(d->draw >> 32); p.sample0 = d->sample0;
-    p.rgb = d->rgb; p.nir = d->nir; p.coords = d->geo ? d->coords : nullptr; p.window = d->window; p.rows = d->window;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(scene_scaled_draw_kernel, dim3((d->B + 255) / 256), dim3(256), 0, st, p);
-    launch_gather(p, d->dtype, p.factor[d->K - 1], st);                         // the factors rise: the last is the largest
-    return nirgan_check_launch(who);
-}
-
-// The gather of the samplers on a list of windows the CALLER names.  The pixels are scene_scaled_gather_kernel's, the
-// same instances: with K = 1 it reads table 0 for every row, whatever the row's factor, and a row's factor only picks the block
-// routine.  The coords are sp_centre's, one thread per row.
-namespace {
-
+// the coords of nirgan_scene_gather's rows, one thread per row (the samplers' draw writes its own)
 struct CentreP {
     const double* geo; const int32_t* rows; float* coords;
     int n, T;
@@ -306,23 +300,126 @@ __global__ __launch_bounds__(256) void scene_gather_centre_kernel(const CentreP 
     sp_centre(p.geo + int64_t(win[0]) * 4, win[1], win[2], f * p.T, p.coords + int64_t(i) * 2);
 }
 
-}  // namespace
+// ---- the host side: what the four descriptors share is checked and filled once; D is the entry's descriptor type ----
 
-extern "C" int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stream) {
-    static const char* who = "scene_gather";
-    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->window && d->window_host && d->rgb && d->nir, "%s: null pointer", who);
+template <typename D> constexpr bool names_rows = std::is_same<D, nirgan_scene_gather_desc>::value;    // no draw: n rows, not B samples
+
+// The checks every entry opens with, in the order every entry has always made them.  own_ptrs: the entry's pointers beyond those
+// of all four.  nirgan_scene_gather has no views, max_invalid or prefix_elems, and places its rows among its window list here.
+template <typename D>
+int check_common(const char* who, const D* d, bool own_ptrs) {
+    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->rgb && d->nir && d->window && own_ptrs, "%s: null pointer", who);
     NG_REQUIRE(d->dtype == NIRGAN_SCENE_U16 || d->dtype == NIRGAN_SCENE_F32, "%s: unknown dtype %d", who, d->dtype);
     NG_REQUIRE(d->S > 0 && d->C >= 4, "%s: bad pool (S %d, C %d; C must be at least 4)", who, d->S, d->C);
+    if constexpr (!names_rows<D>) NG_REQUIRE(d->views == 1 || d->views == 4 || d->views == 8, "%s: views %d is not 1, 4 or 8", who, d->views);
     for (int k = 0; k < 4; ++k) NG_REQUIRE(d->band[k] >= 0 && d->band[k] < d->C, "%s: band %d outside 0 .. C-1", who, d->band[k]);
     const int64_t T = d->tile;
-    NG_REQUIRE(d->n > 0 && T > 0 && T * T < LIM31 && T * T * d->n < LIM31, "%s: n, tile or n*tile*tile is not in 1 .. 2^31-1 (n %d, tile %d)", who, d->n, d->tile);
-    NG_REQUIRE(d->first >= 0 && d->n_windows >= d->n && d->first <= d->n_windows - d->n,
-               "%s: first %lld, n %d: the rows are not inside 0 .. n_windows-1 (n_windows %lld)", who, (long long)d->first, d->n, (long long)d->n_windows);
+    int n;
+    if constexpr (names_rows<D>) n = d->n; else n = d->B;
+    const char* nn = names_rows<D> ? "n" : "B";
+    NG_REQUIRE(n > 0 && T > 0 && T * T < LIM31 && T * T * n < LIM31, "%s: %s, tile or %s*tile*tile is not in 1 .. 2^31-1 (%s %d, tile %d)", who, nn, nn, nn, n, d->tile);
+    if constexpr (names_rows<D>)
+        NG_REQUIRE(d->first >= 0 && d->n_windows >= d->n && d->first <= d->n_windows - d->n,
+                   "%s: first %lld, n %d: the rows are not inside 0 .. n_windows-1 (n_windows %lld)", who, (long long)d->first, d->n, (long long)d->n_windows);
     NG_REQUIRE(d->divisor == d->divisor && d->divisor != 0.0f, "%s: divisor is 0 or NaN", who);
-    for (int s = 0; s < d->S; ++s) {
-        const int64_t* r = d->table_host + int64_t(s) * TC;
-        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
+    if constexpr (!names_rows<D>) {
+        NG_REQUIRE(d->max_invalid >= 0, "%s: negative max_invalid", who);
+        NG_REQUIRE(d->pool_elems >= 0 && d->prefix_elems >= 0, "%s: negative pool_elems or prefix_elems", who);
     }
+    return NIRGAN_OK;
+}
+
+// K factors and their weights into the draw's block: factor, cumw, wtot, K
+int check_scales(const char* who, int K, const int* factor, const uint32_t* weight, int64_t T, DrawCommon& p) {
+    NG_REQUIRE(K >= 1 && K <= MAXK, "%s: K %d outside 1 .. %d", who, K, MAXK);
+    uint64_t wtot = 0;
+    for (int k = 0; k < K; ++k) {
+        const int f = factor[k];
+        NG_REQUIRE(f >= 1 && f <= MAXF, "%s: factor %d outside 1 .. %d", who, f, MAXF);
+        NG_REQUIRE(k == 0 || f > factor[k - 1], "%s: the factors are not strictly increasing (%d after %d)", who, f, factor[k - 1]);
+        NG_REQUIRE(weight[k] > 0, "%s: the weight of factor %d is 0", who, f);
+        wtot += weight[k];
+        NG_REQUIRE(wtot < (uint64_t(1) << 32), "%s: the weights sum to 2^32 or more", who);
+        NG_REQUIRE(f * T * f * T < LIM31, "%s: the window of factor %d, (factor*tile)^2, is 2^31 or more", who, f);
+        p.factor[k] = f;
+        p.cumw[k] = uint32_t(wtot);
+    }
+    p.K = K;
+    p.wtot = uint32_t(wtot);
+    return NIRGAN_OK;
+}
+
+// the gather of n rows on the entry's ONE [S][TC] table (K = 1); nirgan_scene_sample_scaled then names its K tables
+template <typename D>
+GatherP gather_one_table(const D* d, int n, const int32_t* rows) {
+    GatherP g = {};
+    g.pool = d->pool; g.table = d->table;
+    for (int k = 0; k < 4; ++k) g.band[k] = d->band[k];
+    g.K = 1; g.S = d->S; g.T = d->tile;
+    g.nb = (d->tile + SP_B - 1) / SP_B;
+    g.nblk = int64_t(n) * 4 * g.nb * g.nb;
+    g.divisor = d->divisor;
+    g.rgb = d->rgb; g.nir = d->nir;
+    g.rows = rows;
+    return g;
+}
+
+// The two launches of a sampler.  p holds the source's fields, the scales and their totals; the rest of the draw comes from the
+// descriptor.
+template <typename D, typename Source>
+int launch_sampler(const char* who, const D* d, DrawP<Source>& p, const GatherP& g, void* stream) {
+    p.prefix = d->prefix; p.geo = d->geo;
+    p.T = d->tile; p.B = d->B; p.views = d->views; p.max_invalid = d->max_invalid;
+    p.seed_lo = d->seed_lo; p.seed_hi = d->seed_hi; p.draw_lo = uint32_t(d->draw); p.draw_hi = uint32_t(d->draw >> 32); p.sample0 = d->sample0;
+    p.coords = d->geo ? d->coords : nullptr; p.window = d->window;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(scene_draw_kernel<Source>, dim3((d->B + 255) / 256), dim3(256), 0, st, p);
+    launch_gather(g, d->dtype, p.factor[p.K - 1], st);                          // the factors rise: the last is the largest
+    return nirgan_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int nirgan_scene_sample(const nirgan_scene_sample_desc* d, void* stream) {
+    static const char* who = "scene_sample";
+    static const int factor[1] = {1};
+    static const uint32_t weight[1] = {1};
+    if (int e = check_common(who, d, true)) return e;
+    DrawP<Scenes> p = {};
+    p.table = d->table; p.S = d->S;
+    if (int e = check_scales(who, 1, factor, weight, d->tile, p)) return e;
+    if (int e = sp_check_table(who, d->table_host, d->S, d->tile, &p.total[0])) return e;
+    NG_REQUIRE(p.total[0] > 0, "%s: no scene holds a window of tile %d", who, d->tile);
+    if (int e = sp_check_extents(who, d->table_host, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
+    return launch_sampler(who, d, p, gather_one_table(d, d->B, d->window), stream);
+}
+
+extern "C" int nirgan_scene_sample_scaled(const nirgan_scene_scaled_desc* d, void* stream) {
+    static const char* who = "scene_sample_scaled";
+    if (int e = check_common(who, d, true)) return e;
+    const int64_t T = d->tile;
+    DrawP<Scenes> p = {};
+    p.table = d->table; p.S = d->S;
+    if (int e = check_scales(who, d->K, d->factor, d->weight, T, p)) return e;
+    for (int k = 0; k < d->K; ++k) {
+        const int64_t* th = d->table_host + int64_t(k) * d->S * TC;
+        if (int e = sp_check_table(who, th, d->S, p.factor[k] * T, &p.total[k])) return e;
+        NG_REQUIRE(p.total[k] > 0, "%s: no scene holds a window of factor %d (side %lld)", who, p.factor[k], (long long)(p.factor[k] * T));
+        if (int e = sp_check_extents(who, th, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
+    }
+    GatherP g = gather_one_table(d, d->B, d->window);
+    g.K = d->K;
+    for (int k = 0; k < d->K; ++k) g.factor[k] = p.factor[k];
+    return launch_sampler(who, d, p, g, stream);
+}
+
+// The gather on a list of windows the CALLER names: K = 1, table 0 for every row, and a row's factor only picks the
+// block routine.
+extern "C" int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stream) {
+    static const char* who = "scene_gather";
+    if (int e = check_common(who, d, d && d->window_host)) return e;
+    const int64_t T = d->tile;
+    if (int e = sp_check_sides(who, d->table_host, 0, d->S)) return e;
     if (int e = sp_check_extents(who, d->table_host, d->S, d->C, d->pool_elems, nullptr, 0, false)) return e;
     int fmax = 1;
     for (int64_t i = d->first; i < d->first + d->n; ++i) {
@@ -339,105 +436,26 @@ extern "C" int nirgan_scene_gather(const nirgan_scene_gather_desc* d, void* stre
                    (long long)r[1], (long long)r[2]);
         if (f > fmax) fmax = f;
     }
-    ScaledP p = {};
-    p.pool = d->pool; p.table = d->table;
-    for (int k = 0; k < 4; ++k) p.band[k] = d->band[k];
-    p.K = 1; p.S = d->S; p.T = d->tile; p.B = d->n;
-    p.nb = (d->tile + SP_B - 1) / SP_B;
-    p.nblk = int64_t(d->n) * 4 * p.nb * p.nb;
-    p.divisor = d->divisor;
-    p.rgb = d->rgb; p.nir = d->nir;
-    p.rows = d->window + d->first * 4;
+    const GatherP g = gather_one_table(d, d->n, d->window + d->first * 4);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->geo && d->coords) {
-        const CentreP c = {d->geo, p.rows, d->coords, d->n, d->tile};
+        const CentreP c = {d->geo, g.rows, d->coords, d->n, d->tile};
         hipLaunchKernelGGL(scene_gather_centre_kernel, dim3((d->n + 255) / 256), dim3(256), 0, st, c);
     }
-    launch_gather(p, d->dtype, fmax, st);
+    launch_gather(g, d->dtype, fmax, st);
     return nirgan_check_launch(who);
 }
 
-// The draw from a table of rectangles of window origins: nirgan_scene_sample_origins.  Its own parameter block and its
-// own attempt (so_attempt of scene_dev.h); the scale is picked as scene_scaled_draw_kernel picks it, the window word and the coords
-// are written as there, and the pixels are scene_scaled_gather_kernel's on the rows the draw wrote, launched as nirgan_scene_gather
-// launches it: K = 1, the one scene table for every row.
-namespace {
-
-struct OriginsP {
-    const int64_t* table;                // [S][TC]: W_s and the prefix offset are read
-    const int64_t* origins;              // [R][OC]
-    const int32_t* prefix;
-    const double* geo;
-    int64_t total[MAXK];                 // origins of scale k: the cum of its last row
-    int first[MAXK], count[MAXK];
-    int factor[MAXK];
-    uint32_t cumw[MAXK], wtot;
-    int K, T, B, views, max_invalid;
-    uint32_t seed_lo, seed_hi, draw_lo, draw_hi, sample0;
-    float* coords;
-    int32_t* window;
-};
-
-__global__ __launch_bounds__(256) void scene_origins_draw_kernel(const OriginsP p) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= p.B) return;
-    uint32_t w[4];
-    philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), 0u, p.seed_lo, p.seed_hi, w);
-    const uint32_t pick = uint32_t((uint64_t(w[3]) * uint64_t(p.wtot)) >> 32);             // floor(w3 * Wtot / 2^32) < Wtot
-    int f = p.factor[0], first = p.first[0], count = p.count[0];
-    int64_t total = p.total[0];
-#pragma unroll
-    for (int j = 1; j < MAXK; ++j)       // cumw rises: the last j with cumw[j-1] <= pick is the first with cumw[j] > pick
-        if (j < p.K && p.cumw[j - 1] <= pick) { f = p.factor[j]; first = p.first[j]; count = p.count[j]; total = p.total[j]; }
-    const int L = f * p.T;
-    const int64_t* __restrict__ rows = p.origins + int64_t(first) * OC;
-    const int64_t most = int64_t(p.max_invalid) * f * f;
-    int s = 0, y0 = 0, x0 = 0, view = 0, a = 0;
-    bool ok = false;
-    for (; a < NIRGAN_SCENE_ATTEMPTS; ++a) {
-        if (a > 0) philox4x32_10(p.draw_lo, p.draw_hi, p.sample0 + uint32_t(b), uint32_t(a), p.seed_lo, p.seed_hi, w);
-        const int64_t n = so_attempt(w, p.table, rows, count, p.prefix, L, total, p.views, s, y0, x0, view);
-        if (n <= most) { ok = true; break; }
-    }
-    if (!ok) a = NIRGAN_SCENE_ATTEMPTS - 1;
-    int32_t* __restrict__ o = p.window + int64_t(b) * 4;
-    o[0] = s; o[1] = y0; o[2] = x0;
-    o[3] = int32_t(uint32_t(view) | (uint32_t(a) << 8) | (uint32_t(f - 1) << 16) | (ok ? 0u : 0x80000000u));
-    if (p.geo && p.coords) sp_centre(p.geo + int64_t(s) * 4, y0, x0, L, p.coords + int64_t(b) * 2);
-}
-
-}  // namespace
-
+// The draw from a table of rectangles of window origins; the gather runs on the rows the draw wrote as
+// nirgan_scene_gather runs it: the one scene table for every row.
 extern "C" int nirgan_scene_sample_origins(const nirgan_scene_origins_desc* d, void* stream) {
     static const char* who = "scene_sample_origins";
-    NG_REQUIRE(d && d->pool && d->table && d->table_host && d->origins && d->origins_host && d->rgb && d->nir && d->window, "%s: null pointer", who);
-    NG_REQUIRE(d->dtype == NIRGAN_SCENE_U16 || d->dtype == NIRGAN_SCENE_F32, "%s: unknown dtype %d", who, d->dtype);
-    NG_REQUIRE(d->S > 0 && d->C >= 4, "%s: bad pool (S %d, C %d; C must be at least 4)", who, d->S, d->C);
-    NG_REQUIRE(d->views == 1 || d->views == 4 || d->views == 8, "%s: views %d is not 1, 4 or 8", who, d->views);
-    for (int k = 0; k < 4; ++k) NG_REQUIRE(d->band[k] >= 0 && d->band[k] < d->C, "%s: band %d outside 0 .. C-1", who, d->band[k]);
+    if (int e = check_common(who, d, d && d->origins && d->origins_host)) return e;
     const int64_t T = d->tile;
-    NG_REQUIRE(d->B > 0 && T > 0 && T * T < LIM31 && T * T * d->B < LIM31, "%s: B, tile or B*tile*tile is not in 1 .. 2^31-1 (B %d, tile %d)", who, d->B, d->tile);
-    NG_REQUIRE(d->divisor == d->divisor && d->divisor != 0.0f, "%s: divisor is 0 or NaN", who);
-    NG_REQUIRE(d->max_invalid >= 0, "%s: negative max_invalid", who);
-    NG_REQUIRE(d->pool_elems >= 0 && d->prefix_elems >= 0, "%s: negative pool_elems or prefix_elems", who);
-    NG_REQUIRE(d->K >= 1 && d->K <= MAXK, "%s: K %d outside 1 .. %d", who, d->K, MAXK);
-    OriginsP p;
-    uint64_t wtot = 0;
-    for (int k = 0; k < d->K; ++k) {
-        const int f = d->factor[k];
-        NG_REQUIRE(f >= 1 && f <= MAXF, "%s: factor %d outside 1 .. %d", who, f, MAXF);
-        NG_REQUIRE(k == 0 || f > d->factor[k - 1], "%s: the factors are not strictly increasing (%d after %d)", who, f, d->factor[k - 1]);
-        NG_REQUIRE(d->weight[k] > 0, "%s: the weight of factor %d is 0", who, f);
-        wtot += d->weight[k];
-        NG_REQUIRE(wtot < (uint64_t(1) << 32), "%s: the weights sum to 2^32 or more", who);
-        NG_REQUIRE(f * T * f * T < LIM31, "%s: the window of factor %d, (factor*tile)^2, is 2^31 or more", who, f);
-        p.factor[k] = f;
-        p.cumw[k] = uint32_t(wtot);
-    }
-    for (int s = 0; s < d->S; ++s) {
-        const int64_t* r = d->table_host + int64_t(s) * TC;
-        NG_REQUIRE(r[1] > 0 && r[1] < LIM31 && r[2] > 0 && r[2] < LIM31, "%s: scene %d has an extent outside 1 .. 2^31-1", who, s);
-    }
+    DrawP<Origins> p = {};
+    p.table = d->table; p.origins = d->origins;
+    if (int e = check_scales(who, d->K, d->factor, d->weight, T, p)) return e;
+    if (int e = sp_check_sides(who, d->table_host, 0, d->S)) return e;
     if (int e = sp_check_extents(who, d->table_host, d->S, d->C, d->pool_elems, d->prefix, d->prefix_elems)) return e;
     NG_REQUIRE(d->R >= 1, "%s: R %d: the origin table has no row", who, d->R);
     int64_t next = 0;
@@ -470,23 +488,6 @@ extern "C" int nirgan_scene_sample_origins(const nirgan_scene_origins_desc* d, v
         p.first[k] = d->first[k];
         p.count[k] = d->count[k];
     }
-    p.wtot = uint32_t(wtot);
-    for (int k = d->K; k < MAXK; ++k) { p.factor[k] = 0; p.cumw[k] = 0; p.total[k] = 0; p.first[k] = 0; p.count[k] = 0; }
-    p.table = d->table; p.origins = d->origins; p.prefix = d->prefix; p.geo = d->geo;
-    p.K = d->K; p.T = d->tile; p.B = d->B; p.views = d->views; p.max_invalid = d->max_invalid;
-    p.seed_lo = d->seed_lo; p.seed_hi = d->seed_hi; p.draw_lo = uint32_t(d->draw); p.draw_hi = uint32_t(d->draw >> 32); p.sample0 = d->sample0;
-    p.coords = d->geo ? d->coords : nullptr; p.window = d->window;
-    ScaledP g = {};                                                             // the gather's block, as nirgan_scene_gather fills it
-    g.pool = d->pool; g.table = d->table;
-    for (int k = 0; k < 4; ++k) g.band[k] = d->band[k];
-    g.K = 1; g.S = d->S; g.T = d->tile; g.B = d->B;
-    g.nb = (d->tile + SP_B - 1) / SP_B;
-    g.nblk = int64_t(d->B) * 4 * g.nb * g.nb;
-    g.divisor = d->divisor;
-    g.rgb = d->rgb; g.nir = d->nir;
-    g.rows = d->window;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(scene_origins_draw_kernel, dim3((d->B + 255) / 256), dim3(256), 0, st, p);
-    launch_gather(g, d->dtype, p.factor[d->K - 1], st);                         // the factors rise: the last is the largest
-    return nirgan_check_launch(who);
+    return launch_sampler(who, d, p, gather_one_table(d, d->B, d->window), stream);
 }
+

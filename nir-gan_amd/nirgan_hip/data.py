@@ -1,4 +1,4 @@
-"""Training batches from device-resident scenes: the sampler of csrc/scenepool.hip seen from Python.
+"""Training batches from device-resident scenes: the entries of csrc/scenesample.hip seen from Python.
 
 The reference reads a tile per item through rasterio, ``.astype(np.float32) / 10000``, bands 0..2 = RGB, band 3 = NIR, ``coords`` =
 lon / lat of the centre pixel (data/SR_dataset_RGB.py:24-56).  Here the scenes are uploaded ONCE as they are stored (uint16 or
@@ -64,7 +64,121 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
 
 
-class ScenePool:
+def _is_integer(x, lo) -> bool:
+    """whether ``x`` is an integer -- no bool, no fraction -- of at least ``lo``"""
+    return not isinstance(x, bool) and x == int(x) and int(x) >= lo
+
+
+def _side(what, f, tile) -> int:
+    """the side ``f * tile`` of the source window of ``what`` (scale / factor) f; the entries take windows below 2^31 pixels"""
+    if (f * tile) ** 2 >= 2 ** 31:
+        raise ValueError(f"{what} {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
+    return f * tile
+
+
+def _fill(d, pool, table, out, tile, draw=None):
+    """The descriptor fields every scene entry shares: pool, table (device, host), geo, band, tile, divisor and the outputs; with
+    ``draw`` = (B, augment, seed, draw, sample0, max_invalid) also what the three samplers share beyond that."""
+    d.pool, d.pool_elems, d.dtype, d.S, d.C = pool.pool.data_ptr(), pool.pool_elems, pool.dtype, len(pool.shapes), pool.C
+    d.table, d.table_host = table[0].data_ptr(), table[1].ctypes.data
+    d.geo = pool.geo.data_ptr() if pool.geo is not None else None
+    d.band = (C.c_int * 4)(*pool.bands)
+    d.tile, d.divisor = tile, pool.divisor
+    d.rgb, d.nir = out["rgb"].data_ptr(), out["nir"].data_ptr()
+    d.coords = out["coords"].data_ptr() if pool.geo is not None else None
+    if draw is not None:
+        d.B, augment, seed, number, sample0, max_invalid = draw
+        d.prefix, d.prefix_elems = (pool.prefix.data_ptr() if pool.prefix is not None else None), pool.prefix_elems
+        d.views = L.SCENE_VIEWS[augment]
+        d.seed_lo, d.seed_hi = split_seed(seed)
+        d.draw, d.sample0, d.max_invalid = int(number) & ((1 << 64) - 1), int(sample0) & 0xFFFFFFFF, int(max_invalid)
+        d.window = out["window"].data_ptr()
+
+
+def _fill_scales(d, factors, weights):
+    d.K = len(factors)
+    d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
+
+
+class _Sampler:
+    """``sample`` and ``loader`` of ``ScenePool`` and ``SplitTrain``.  A subclass has a ``device``, makes the output tensors in
+    ``_outputs`` and names its entry and descriptor in ``_describe``."""
+
+    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
+               scales=None, scale_weights=None):
+        """One batch ``{"rgb" [B,3,T,T], "nir" [B,1,T,T][, "coords" [B,2]]}``, plus ``"window"`` [B,4] int32 = (scene, y0, x0,
+        view | attempt << 8 | (factor - 1) << 16 | exhausted << 31) with ``return_windows``.  Sample b is a function of ``(seed, draw,
+        sample0 + b)`` alone.  ``augment``: "d4" (8 views), "flips" (4) or "none".  ``max_invalid``: the most invalid pixels a window
+        may hold (only with ``nodata``); after 8 rejected attempts the last window is returned and bit 31 of its window word is set.
+        ``out``: the tensors to write into (the dict of an earlier call with ``return_windows`` and the same shapes) instead of new ones.
+        ``scales``: distinct resolution factors in 1 .. 8 (sorted before use), one drawn per sample with the positive integer
+        ``scale_weights`` (default: all 1); the sample is then an f*T window of the source (y0, x0 in source pixels, ``max_invalid``
+        per f x f block, coords of the window's centre) delivered as the T x T tile of its f x f block means.  None: factor 1 -- a
+        ``ScenePool`` through ``nirgan_scene_sample``, as ever; a ``SplitTrain`` through its one entry."""
+        if augment not in L.SCENE_VIEWS:
+            raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
+        B, tile = int(batch_size), int(tile)
+        if B <= 0 or tile <= 0:
+            raise ValueError("batch_size and tile must be positive")
+        out = out if out is not None else self._outputs(B, tile)
+        entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
+        L.call(entry, C.byref(d), _stream(self.device))
+        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
+
+    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
+               scale_weights=None):
+        """``SceneLoader`` over this source: it only asks for ``_outputs`` and ``sample``"""
+        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
+                           world=world, scales=scales, scale_weights=scale_weights)
+
+
+def _grid(pool, regions, tile, factors, stride, max_invalid, cover, nothing_left):
+    """The grid of ``ScenePool.grid`` over regions ``(scene, y0, x0, h, w)``: whole scenes there, held-out rectangles in
+    ``SplitVal.grid``.  ``regions``: a callable, asked once the other arguments have passed; ``nothing_left``: how the ValueError of an
+    empty grid ends."""
+    tile = int(tile)
+    if tile <= 0:
+        raise ValueError("tile must be positive")
+    factors, _ = check_scales(factors)
+    if stride is not None and not _is_integer(stride, 1):
+        raise ValueError(f"stride must be an integer of at least 1 (source pixels), got {stride!r}")
+    if not _is_integer(max_invalid, 0):
+        raise ValueError(f"max_invalid must be a non-negative integer, got {max_invalid!r}")
+    regions = regions()
+    parts, keeps = [], []
+    for f in factors:
+        side = _side("factor", f, tile)
+        step = side if stride is None else int(stride)
+        for s, y0, x0, h, w in regions:
+            if h < side or w < side:
+                continue
+            yy, xx = np.meshgrid(y0 + _grid_starts(h, side, step, cover), x0 + _grid_starts(w, side, step, cover), indexing="ij")
+            part = np.empty((yy.size, 4), dtype=np.int32)
+            part[:, 0], part[:, 1], part[:, 2], part[:, 3] = s, yy.reshape(-1), xx.reshape(-1), (f - 1) << 16
+            parts.append(part)
+            if pool.prefix is not None:
+                P = pool.invalid_prefix(s)
+                y, x = (torch.from_numpy(part[:, c].astype(np.int64)).to(pool.device) for c in (1, 2))
+                count = P[y + side, x + side].long() - P[y, x + side].long() - P[y + side, x].long() + P[y, x].long()
+                keeps.append(count <= int(max_invalid) * f * f)
+    rows = np.concatenate(parts) if parts else np.empty((0, 4), dtype=np.int32)
+    if keeps:
+        rows = rows[torch.cat(keeps).cpu().numpy()]                              # the one copy to the host
+    if not len(rows):
+        raise ValueError(f"the grid is empty: no window of tile {tile} at factors {factors} {nothing_left}")
+    return WindowList(rows, pool.device)
+
+
+def _grid_loader(pool, grid, batch_size, tile, rank, world, **kw):
+    """``GridLoader`` over this rank's rows of ``grid(tile, **kw)``: the rows i with ``i % world == rank``, in order"""
+    if not 0 <= int(rank) < int(world):
+        raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
+    full = grid(tile, **kw)
+    mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], pool.device)
+    return GridLoader(pool, mine, batch_size, tile)
+
+
+class ScenePool(_Sampler):
     """``scenes``: a list of [C, H, W] arrays or tensors, all uint16 or all float32, with one C >= 4; uploaded once into one exactly
     sized device buffer.  ``bands``: the source planes of R, G, B, NIR.  ``divisor``: what every value is divided by (float32).
     ``nodata``: if given, a pixel is invalid where any selected band equals it (uint16) or is NaN (float32; the value itself is not
@@ -189,66 +303,26 @@ class ScenePool:
             out["coords"] = torch.empty((B, 2), dtype=torch.float32, device=self.device)
         return out
 
-    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
-               scales=None, scale_weights=None):
-        """One batch ``{"rgb" [B,3,T,T], "nir" [B,1,T,T][, "coords" [B,2]]}``, plus ``"window"`` [B,4] int32 = (scene, y0, x0,
-        view | attempt << 8 | (factor - 1) << 16 | exhausted << 31) with ``return_windows``.  Sample b is a function of ``(seed, draw,
-        sample0 + b)`` alone.  ``augment``: "d4" (8 views), "flips" (4) or "none".  ``max_invalid``: the most invalid pixels a window
-        may hold (only with ``nodata``); after 8 rejected attempts the last window is returned and bit 31 of its window word is set.
-        ``out``: the tensors to write into (the dict of an earlier call with ``return_windows`` and the same shapes) instead of new ones.
-        ``scales``: distinct resolution factors in 1 .. 8 (sorted before use), one drawn per sample with the positive integer
-        ``scale_weights`` (default: all 1); the sample is then an f*T window of the source (y0, x0 in source pixels, ``max_invalid``
-        per f x f block, coords of the window's centre) delivered as the T x T tile of its f x f block means.  None: factor 1
-        through ``nirgan_scene_sample``, as ever."""
-        if augment not in L.SCENE_VIEWS:
-            raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
-        B, tile = int(batch_size), int(tile)
-        if B <= 0 or tile <= 0:
-            raise ValueError("batch_size and tile must be positive")
-        out = out if out is not None else self._outputs(B, tile)
-        entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
-        L.call(entry, C.byref(d), _stream(self.device))
-        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
-
     def _describe(self, out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights):
         """(name of the entry, its descriptor) of one checked ``sample`` call writing into ``out``"""
         if scales is None:
             if scale_weights is not None:
                 raise ValueError("scale_weights without scales")
-            d = L.SceneSampleDesc()
-            table, table_host = self._table(tile)
-            if int(table_host[-1, 3]) == 0:
+            entry, d, table = "nirgan_scene_sample", L.SceneSampleDesc(), self._table(tile)
+            if int(table[1][-1, 3]) == 0:
                 raise ValueError(f"no scene of the pool holds a {tile} x {tile} window")
-            entry = "nirgan_scene_sample"
         else:
-            d = L.SceneScaledDesc()
+            entry, d = "nirgan_scene_sample_scaled", L.SceneScaledDesc()
             factors, weights = check_scales(scales, scale_weights)
             for f in factors:
-                if (f * tile) ** 2 >= 2 ** 31:
-                    raise ValueError(f"scale {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
-            table, table_host = self._scaled_tables(tile, factors)
-            for f, t in zip(factors, table_host):
+                _side("scale", f, tile)
+            table = self._scaled_tables(tile, factors)
+            for f, t in zip(factors, table[1]):
                 if int(t[-1, 3]) == 0:
                     raise ValueError(f"scale {f}: no scene of the pool holds a {f * tile} x {f * tile} window")
-            d.K = len(factors)
-            d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
-            entry = "nirgan_scene_sample_scaled"
-        d.pool, d.pool_elems, d.dtype, d.S, d.C = self.pool.data_ptr(), self.pool_elems, self.dtype, len(self.shapes), self.C
-        d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
-        d.prefix, d.prefix_elems = (self.prefix.data_ptr() if self.prefix is not None else None), self.prefix_elems
-        d.geo = self.geo.data_ptr() if self.geo is not None else None
-        d.band = (C.c_int * 4)(*self.bands)
-        d.tile, d.B, d.views, d.divisor = tile, B, L.SCENE_VIEWS[augment], self.divisor
-        d.seed_lo, d.seed_hi = split_seed(seed)
-        d.draw, d.sample0, d.max_invalid = int(draw) & ((1 << 64) - 1), int(sample0) & 0xFFFFFFFF, int(max_invalid)
-        d.rgb, d.nir, d.window = out["rgb"].data_ptr(), out["nir"].data_ptr(), out["window"].data_ptr()
-        d.coords = out["coords"].data_ptr() if self.geo is not None else None
+            _fill_scales(d, factors, weights)
+        _fill(d, self, table, out, tile, (B, augment, seed, draw, sample0, max_invalid))
         return entry, d
-
-    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
-               scale_weights=None):
-        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
-                           world=world, scales=scales, scale_weights=scale_weights)
 
     def grid(self, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None) -> "WindowList":
         """A fixed, deterministic list of windows over the scenes, for ``gather`` and ``grid_loader``.  ``factors``:
@@ -261,42 +335,12 @@ class ScenePool:
         Every word is ``(f - 1) << 16``: view 0.  The filter runs on the device on the scenes' prefix tables (four gathers per scene
         and factor) and its verdicts come back in ONE copy, the only synchronisation; a pool without ``nodata`` needs none.
         ValueError if no window is left."""
-        tile = int(tile)
-        if tile <= 0:
-            raise ValueError("tile must be positive")
-        factors, _ = check_scales(factors)
-        if stride is not None and (isinstance(stride, bool) or stride != int(stride) or int(stride) < 1):
-            raise ValueError(f"stride must be an integer of at least 1 (source pixels), got {stride!r}")
-        if isinstance(max_invalid, bool) or max_invalid != int(max_invalid) or int(max_invalid) < 0:
-            raise ValueError(f"max_invalid must be a non-negative integer, got {max_invalid!r}")
-        ids = list(range(len(self.shapes))) if scenes is None else [int(s) for s in scenes]
-        if any(not 0 <= s < len(self.shapes) for s in ids):
-            raise ValueError(f"scenes must name scenes in 0 .. {len(self.shapes) - 1}, got {list(scenes)}")
-        parts, keeps = [], []
-        for f in factors:
-            side = f * tile
-            if side * side >= 2 ** 31:
-                raise ValueError(f"factor {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
-            step = side if stride is None else int(stride)
-            for s in ids:
-                h, w = self.shapes[s]
-                if h < side or w < side:
-                    continue
-                yy, xx = np.meshgrid(_grid_starts(h, side, step, cover), _grid_starts(w, side, step, cover), indexing="ij")
-                part = np.empty((yy.size, 4), dtype=np.int32)
-                part[:, 0], part[:, 1], part[:, 2], part[:, 3] = s, yy.reshape(-1), xx.reshape(-1), (f - 1) << 16
-                parts.append(part)
-                if self.prefix is not None:
-                    P = self.invalid_prefix(s)
-                    y, x = (torch.from_numpy(part[:, c].astype(np.int64)).to(self.device) for c in (1, 2))
-                    count = P[y + side, x + side].long() - P[y, x + side].long() - P[y + side, x].long() + P[y, x].long()
-                    keeps.append(count <= int(max_invalid) * f * f)
-        rows = np.concatenate(parts) if parts else np.empty((0, 4), dtype=np.int32)
-        if keeps:
-            rows = rows[torch.cat(keeps).cpu().numpy()]                          # the one copy to the host
-        if not len(rows):
-            raise ValueError(f"the grid is empty: no window of tile {tile} at factors {factors} is left on these scenes")
-        return WindowList(rows, self.device)
+        def regions():
+            ids = list(range(len(self.shapes))) if scenes is None else [int(s) for s in scenes]
+            if any(not 0 <= s < len(self.shapes) for s in ids):
+                raise ValueError(f"scenes must name scenes in 0 .. {len(self.shapes) - 1}, got {list(scenes)}")
+            return [(s, 0, 0) + self.shapes[s] for s in ids]
+        return _grid(self, regions, tile, factors, stride, max_invalid, cover, "is left on these scenes")
 
     def gather(self, windows, tile, *, first=0, count=None, out=None):
         """``{"rgb" [n,3,T,T], "nir" [n,1,T,T][, "coords" [n,2]]}`` of the rows ``first .. first + count - 1`` (default: to the end) of
@@ -322,26 +366,16 @@ class ScenePool:
             if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.pool.device or not t.is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous float32 {shape} tensor on {self.pool.device}")
         d = L.SceneGatherDesc()
-        table, table_host = self._table(tile)                                    # columns 0 .. 2 are read: the table of any side will do
-        d.pool, d.pool_elems, d.dtype, d.S, d.C = self.pool.data_ptr(), self.pool_elems, self.dtype, len(self.shapes), self.C
-        d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
-        d.geo = self.geo.data_ptr() if self.geo is not None else None
-        d.band = (C.c_int * 4)(*self.bands)
-        d.tile, d.divisor = tile, self.divisor
+        _fill(d, self, self._table(tile), out, tile)                             # columns 0 .. 2 are read: the table of any side will do
         d.window, d.window_host, d.n_windows, d.first, d.n = wl.device.data_ptr(), wl.host.ctypes.data, len(wl), first, n
-        d.rgb, d.nir = out["rgb"].data_ptr(), out["nir"].data_ptr()
-        d.coords = out["coords"].data_ptr() if self.geo is not None else None
         L.call("nirgan_scene_gather", C.byref(d), _stream(self.device))
         return {k: out[k] for k in ("rgb", "nir", "coords") if k in out and (k != "coords" or self.geo is not None)}
 
     def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None, rank=0, world=1):
         """``GridLoader`` over ``grid(tile, ...)``: a fixed validation set.  Rank ``rank`` of ``world`` takes the rows i of the grid
         with ``i % world == rank``, in order."""
-        if not 0 <= int(rank) < int(world):
-            raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
-        full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover, scenes=scenes)
-        mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
-        return GridLoader(self, mine, batch_size, tile)
+        return _grid_loader(self, self.grid, batch_size, tile, rank, world, factors=factors, stride=stride, max_invalid=max_invalid,
+                            cover=cover, scenes=scenes)
 
     def scene(self, s: int) -> torch.Tensor:
         """Scene ``s`` as a [C, H, W] VIEW of the pool's buffer (int16 bit patterns of a uint16 pool); nothing is copied."""
@@ -375,7 +409,7 @@ class ScenePool:
         those with the smallest ``block_key(seed, s, i, j)``, ties broken by (s, i, j) -- pure Python integers, the same cells on every
         platform.  Adjacent cells of a block row are merged into one rectangle, and runs over the same columns in consecutive block
         rows are stacked."""
-        if isinstance(block, bool) or block != int(block) or int(block) < 1:
+        if not _is_integer(block, 1):
             raise ValueError(f"block must be a positive integer, got {block!r}")
         if not 0.0 < float(val_fraction) < 1.0:
             raise ValueError(f"val_fraction must lie strictly between 0 and 1, got {val_fraction!r}")
@@ -463,7 +497,7 @@ class PoolSplit:
     rectangles (``SplitVal``).  Both read the pool's own device buffers."""
 
     def __init__(self, pool, val, guard=0):
-        if isinstance(guard, bool) or guard != int(guard) or int(guard) < 0:
+        if not _is_integer(guard, 0):
             raise ValueError(f"guard must be a non-negative integer (source pixels), got {guard!r}")
         rects = []
         for r in val:
@@ -503,7 +537,7 @@ class PoolSplit:
         return out
 
 
-class SplitTrain:
+class SplitTrain(_Sampler):
     """The training half of a ``PoolSplit``: ``sample`` / ``loader`` with ``ScenePool``'s signatures, through
     ``nirgan_scene_sample_origins``.  The draw runs over a table of rectangles of admissible window origins, built on the host by
     ``origin_rectangles`` once per ``(tile, factors)``: it is exactly uniform over the admissible windows and cannot name a window
@@ -522,9 +556,7 @@ class SplitTrain:
             rows, first, count = [], [], []
             held = {s: [r[1:] for r in self.split.rectangles if r[0] == s] for s in range(len(self.pool.shapes))}
             for f in key[1]:
-                side, cum = f * key[0], 0
-                if side * side >= 2 ** 31:
-                    raise ValueError(f"scale {f}: the window ({f} * {key[0]})^2 has 2^31 pixels or more")
+                side, cum = _side("scale", f, key[0]), 0
                 first.append(len(rows))
                 for s, shape in enumerate(self.pool.shapes):
                     for oy, ox, oh, ow in origin_rectangles(shape, side, held[s], self.split.guard):
@@ -545,50 +577,20 @@ class SplitTrain:
         """how many windows of side ``factor * tile`` are admissible"""
         return int(self._table(tile, (int(factor),))[1][-1, 5])
 
-    def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
-               scales=None, scale_weights=None):
-        """``ScenePool.sample`` on the admissible windows.  ``scales=None``: factor 1, through the same entry.  After 8 rejected
-        nodata attempts the last window is returned with bit 31 set, as there -- it is an admissible window all the same."""
-        if augment not in L.SCENE_VIEWS:
-            raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
-        B, tile = int(batch_size), int(tile)
-        if B <= 0 or tile <= 0:
-            raise ValueError("batch_size and tile must be positive")
-        out = out if out is not None else self._outputs(B, tile)
-        entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
-        L.call(entry, C.byref(d), _stream(self.device))
-        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
-
     def _describe(self, out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights):
-        """(name of the entry, its descriptor) of one checked ``sample`` call writing into ``out``"""
+        """(name of the entry, its descriptor) of one checked ``sample`` call writing into ``out``: ``ScenePool.sample`` on the
+        admissible windows.  After 8 rejected nodata attempts the last window is returned with bit 31 set, as there -- it is an
+        admissible window all the same."""
         if scales is None and scale_weights is not None:
             raise ValueError("scale_weights without scales")
         factors, weights = check_scales(scales, scale_weights) if scales is not None else ((1,), (1,))
         origins, origins_host, first, count = self._table(tile, factors)
-        pool = self.pool
         d = L.SceneOriginsDesc()
-        table, table_host = pool._table(tile)                                    # columns 0, 1, 2, 4 are read: the table of any side will do
-        d.pool, d.pool_elems, d.dtype, d.S, d.C = pool.pool.data_ptr(), pool.pool_elems, pool.dtype, len(pool.shapes), pool.C
-        d.table, d.table_host = table.data_ptr(), table_host.ctypes.data
-        d.prefix, d.prefix_elems = (pool.prefix.data_ptr() if pool.prefix is not None else None), pool.prefix_elems
-        d.geo = pool.geo.data_ptr() if pool.geo is not None else None
-        d.band = (C.c_int * 4)(*pool.bands)
-        d.tile, d.B, d.views, d.divisor = tile, B, L.SCENE_VIEWS[augment], pool.divisor
-        d.seed_lo, d.seed_hi = split_seed(seed)
-        d.draw, d.sample0, d.max_invalid = int(draw) & ((1 << 64) - 1), int(sample0) & 0xFFFFFFFF, int(max_invalid)
-        d.rgb, d.nir, d.window = out["rgb"].data_ptr(), out["nir"].data_ptr(), out["window"].data_ptr()
-        d.coords = out["coords"].data_ptr() if pool.geo is not None else None
-        d.K = len(factors)
-        d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
+        _fill(d, self.pool, self.pool._table(tile), out, tile, (B, augment, seed, draw, sample0, max_invalid))   # columns 0, 1, 2, 4 are read
+        _fill_scales(d, factors, weights)
         d.origins, d.origins_host, d.R = origins.data_ptr(), origins_host.ctypes.data, len(origins_host)
         d.first, d.count = (C.c_int * 8)(*first), (C.c_int * 8)(*count)
         return "nirgan_scene_sample_origins", d
-
-    def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
-               scale_weights=None):
-        """``SceneLoader`` over this half: it only asks its pool for ``_outputs`` and ``sample``"""
-        return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
-                           world=world, scales=scales, scale_weights=scale_weights)
 
 
 class SplitVal:
@@ -603,38 +605,7 @@ class SplitVal:
         and w >= L gives the rows y0 + 0, stride, 2 * stride, ... <= y0 + h - L (with ``cover`` also y0 + h - L) and the columns by the
         same rule.  Order: factor, then rectangle as given to ``split``, then row, then column.  The nodata filter is the grid's own.
         ValueError if no window is left."""
-        pool, tile = self.pool, int(tile)
-        if tile <= 0:
-            raise ValueError("tile must be positive")
-        factors, _ = check_scales(factors)
-        if stride is not None and (isinstance(stride, bool) or stride != int(stride) or int(stride) < 1):
-            raise ValueError(f"stride must be an integer of at least 1 (source pixels), got {stride!r}")
-        if isinstance(max_invalid, bool) or max_invalid != int(max_invalid) or int(max_invalid) < 0:
-            raise ValueError(f"max_invalid must be a non-negative integer, got {max_invalid!r}")
-        parts, keeps = [], []
-        for f in factors:
-            side = f * tile
-            if side * side >= 2 ** 31:
-                raise ValueError(f"factor {f}: the window ({f} * {tile})^2 has 2^31 pixels or more")
-            step = side if stride is None else int(stride)
-            for s, y0, x0, h, w in self.split.rectangles:
-                if h < side or w < side:
-                    continue
-                yy, xx = np.meshgrid(y0 + _grid_starts(h, side, step, cover), x0 + _grid_starts(w, side, step, cover), indexing="ij")
-                part = np.empty((yy.size, 4), dtype=np.int32)
-                part[:, 0], part[:, 1], part[:, 2], part[:, 3] = s, yy.reshape(-1), xx.reshape(-1), (f - 1) << 16
-                parts.append(part)
-                if pool.prefix is not None:
-                    P = pool.invalid_prefix(s)
-                    y, x = (torch.from_numpy(part[:, c].astype(np.int64)).to(self.device) for c in (1, 2))
-                    n = P[y + side, x + side].long() - P[y, x + side].long() - P[y + side, x].long() + P[y, x].long()
-                    keeps.append(n <= int(max_invalid) * f * f)
-        rows = np.concatenate(parts) if parts else np.empty((0, 4), dtype=np.int32)
-        if keeps:
-            rows = rows[torch.cat(keeps).cpu().numpy()]                          # the one copy to the host
-        if not len(rows):
-            raise ValueError(f"the grid is empty: no window of tile {tile} at factors {factors} lies inside a held-out rectangle")
-        return WindowList(rows, self.device)
+        return _grid(self.pool, lambda: self.split.rectangles, tile, factors, stride, max_invalid, cover, "lies inside a held-out rectangle")
 
     def gather(self, windows, tile, *, first=0, count=None, out=None):
         """``ScenePool.gather``: the rows are cut as they are named, whichever half they came from"""
@@ -642,11 +613,8 @@ class SplitVal:
 
     def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, rank=0, world=1):
         """``GridLoader`` over ``grid(tile, ...)``; rank ``rank`` of ``world`` takes the rows i with ``i % world == rank``, in order"""
-        if not 0 <= int(rank) < int(world):
-            raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
-        full = self.grid(tile, factors=factors, stride=stride, max_invalid=max_invalid, cover=cover)
-        mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], self.device)
-        return GridLoader(self.pool, mine, batch_size, tile)
+        return _grid_loader(self.pool, self.grid, batch_size, tile, rank, world, factors=factors, stride=stride, max_invalid=max_invalid,
+                            cover=cover)
 
 
 def _grid_starts(extent, side, step, cover):
@@ -726,9 +694,9 @@ def check_scales(scales, scale_weights=None):
     if not 1 <= len(pairs) <= L.SCENE_MAX_SCALES:
         raise ValueError(f"scales must name 1 .. {L.SCENE_MAX_SCALES} factors, got {len(pairs)}")
     for f, w in pairs:
-        if isinstance(f, bool) or f != int(f) or not 1 <= int(f) <= L.SCENE_MAX_FACTOR:
+        if not _is_integer(f, 1) or int(f) > L.SCENE_MAX_FACTOR:
             raise ValueError(f"scale {f!r} is not an integer in 1 .. {L.SCENE_MAX_FACTOR}")
-        if isinstance(w, bool) or w != int(w) or int(w) <= 0:
+        if not _is_integer(w, 1):
             raise ValueError(f"scale {f}: the weight {w!r} is not a positive integer")
     pairs = sorted((int(f), int(w)) for f, w in pairs)
     factors, weights = tuple(f for f, _ in pairs), tuple(w for _, w in pairs)

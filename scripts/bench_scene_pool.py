@@ -9,7 +9,9 @@ The pool: `--scenes` uint16 scenes of 4 x `--extent` x `--extent` with nodata = 
 geotransforms given (coords are produced), augment "d4".  Warm-up, then `--steps` timed steps per arm between HIP events, the arms
 interleaved over `--rounds` rounds; median, min and max of the rounds per arm.  `sample_ms` times the two launches of a batch alone,
 back to back, and gives their rate against the bytes they move (uint16 in, float32 out).  Under a kernel trace (rocprofv3
---kernel-trace --stats -- python scripts/bench_scene_pool.py) the kernels are scene_draw_kernel and scene_gather_kernel.
+--kernel-trace --stats -- python scripts/bench_scene_pool.py) the kernels are scene_draw_kernel<Scenes>, the draw all
+sampling entries share, and scene_scaled_gather_kernel<uint16_t, 4> (profiles/scene_pool_timing.json is older: it names the two
+kernels nirgan_scene_sample had to itself then).
 Prints one JSON line.
 
     python scripts/bench_scene_pool.py [--rounds 3] [--steps 20] [--warmup 5] [--bs 16] [--size 256] [--scenes 8] [--extent 2048]

@@ -5,6 +5,10 @@ tests/emu_class_metrics.py (the end of the emulator chain), so one backend serve
 Written from the header alone: Philox4x32-10 from tests/emu_dropout.py, the window index as the high word of a Python-int product,
 ``bisect`` for the scene, ``np.cumsum`` for the prefix table, index arrays for the views, ``np.float32(v) / np.float32(divisor)`` for
 the values and float64 for the coords.  ``draw_windows`` / ``cut`` / ``centre`` are what the test bodies compare the device with.
+
+What the later scene entries (tests/emu_scene_scale.py, emu_scene_grid.py, emu_scene_split.py) share with this one is stated once,
+here: ``entry`` (an emulated entry refuses by raising ``Refused``), the opening checks ``check_common``, the table checks
+``check_sides`` / ``check_cum`` / ``check_extents``, the attempt loop ``draw_rows`` and the delivery loop ``deliver``.
 """
 import bisect
 import ctypes as C
@@ -44,37 +48,46 @@ def window_counts(shapes, T):
     return cum
 
 
-def draw_windows(shapes, T, B, views, seed, draw, sample0=0, prefixes=None, max_invalid=0):
-    """int64 [B][4] = (scene, y0, x0, view | attempt << 8 | exhausted << 31) -- as a non-negative Python value, compare with the
-    device's int32 word after ``& 0xFFFFFFFF``.  shapes: [(H, W)]; prefixes: per scene an [(H+1)][(W+1)] table or None."""
+def draw_rows(B, views, seed, draw, sample0, prefixes, scale_of):
+    """The attempt loop of every draw.  ``scale_of(b)`` = (side, total, most, bits, origin): sample b draws among ``total`` windows of
+    side ``side``, ``origin(idx)`` = (s, y0, x0, tag) names window ``idx`` of them, at most ``most`` invalid pixels are accepted and
+    ``bits`` go into the word.  -> (int64 [B][4] rows of non-negative Python values, the tag of each window taken)"""
     lo, hi = seed if isinstance(seed, (tuple, list)) else (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-    cum = window_counts(shapes, T)
-    total = cum[-1]
-    assert total > 0
-    out = np.zeros((B, 4), dtype=np.int64)
     samples = (np.arange(B, dtype=np.uint64) + np.uint64(sample0 & 0xFFFFFFFF))[:, None]
     words = philox4x32_10((draw & 0xFFFFFFFF, (draw >> 32) & 0xFFFFFFFF, samples, np.arange(ATTEMPTS, dtype=np.uint64)[None, :]), (lo, hi))
     words = np.stack(words, axis=-1).tolist()                                    # [B][ATTEMPTS][4] Python ints
+    out, tags = np.zeros((B, 4), dtype=np.int64), []
     for b in range(B):
+        side, total, most, bits, origin = scale_of(b)
         for a in range(ATTEMPTS):
             w = words[b][a]
-            u = w[0] | (w[1] << 32)
-            idx = (u * total) >> 64
-            s = bisect.bisect_right(cum, idx)                                    # the first scene with cum > idx
-            r = idx - (cum[s - 1] if s else 0)
-            nx = shapes[s][1] - T + 1
-            y0, x0 = r // nx, r % nx
+            s, y0, x0, tag = origin(((w[0] | (w[1] << 32)) * total) >> 64)
             view = w[2] & (views - 1)
             n = 0
             if prefixes is not None and prefixes[s] is not None:
-                P = prefixes[s].astype(np.int64)
-                n = int(P[y0 + T, x0 + T] - P[y0, x0 + T] - P[y0 + T, x0] + P[y0, x0])
-            if n <= max_invalid:
+                P = prefixes[s]
+                n = int(P[y0 + side][x0 + side]) - int(P[y0][x0 + side]) - int(P[y0 + side][x0]) + int(P[y0][x0])
+            if n <= most:
                 break
         else:
             a |= 1 << 23                                                          # exhausted: bit 31 of the word after << 8
-        out[b] = (s, y0, x0, view | (a << 8))
-    return out
+        out[b] = (s, y0, x0, view | (a << 8) | bits)
+        tags.append(tag)
+    return out, tags
+
+
+def draw_windows(shapes, T, B, views, seed, draw, sample0=0, prefixes=None, max_invalid=0):
+    """int64 [B][4] = (scene, y0, x0, view | attempt << 8 | exhausted << 31) -- as a non-negative Python value, compare with the
+    device's int32 word after ``& 0xFFFFFFFF``.  shapes: [(H, W)]; prefixes: per scene an [(H+1)][(W+1)] table or None."""
+    cum = window_counts(shapes, T)
+    assert cum[-1] > 0
+
+    def origin(idx):
+        s = bisect.bisect_right(cum, idx)                                        # the first scene with cum > idx
+        r = idx - (cum[s - 1] if s else 0)
+        nx = shapes[s][1] - T + 1
+        return s, r // nx, r % nx, None
+    return draw_rows(B, views, seed, draw, sample0, prefixes, lambda b: (T, cum[-1], max_invalid, 0, origin))[0]
 
 
 def view_index(g, T):
@@ -108,95 +121,131 @@ def _i64(ptr, n):
     return np.ctypeslib.as_array((C.c_int64 * int(n)).from_address(int(ptr)))
 
 
+class Refused(Exception):
+    """an argument error of an emulated entry; ``entry`` turns it into the library's failure"""
+
+
+def need(ok, msg):
+    if not ok:
+        raise Refused(msg)
+
+
+def entry(who):
+    """an emulated entry from ``body(self, d)``: the call is logged, a null descriptor and every ``Refused`` fail as ``who: message``"""
+    def wrap(body):
+        def call(self, ref, stream=None):
+            self.calls.append(who)
+            try:
+                need(ref, "null pointer")
+                body(self, obj(ref))
+            except Refused as e:
+                return self._fail(f"{who}: {e}")
+            return 0
+        return call
+    return wrap
+
+
+def check_common(d, own_ptrs=(), n="B"):
+    """the checks every entry opens with -> (T, n); an entry of ``n`` rows instead of ``B`` samples has no views, max_invalid or
+    prefix_elems and places its rows inside its list here"""
+    need(all(getattr(d, p) for p in ("pool", "table", "table_host", "rgb", "nir", "window") + own_ptrs), "null pointer")
+    need(d.dtype in (0, 1), "unknown dtype")
+    need(d.S > 0 and d.C >= 4, "bad pool (C must be at least 4)")
+    need(n != "B" or d.views in (1, 4, 8), f"views {getattr(d, 'views', None)} is not 1, 4 or 8")
+    need(all(0 <= b < d.C for b in d.band), "band outside 0 .. C-1")
+    T, N = int(d.tile), int(getattr(d, n))
+    need(N > 0 and T > 0 and T * T < 2 ** 31 and N * T * T < 2 ** 31, f"{n}, tile or {n}*tile*tile is not in 1 .. 2^31-1")
+    if n != "B":
+        need(0 <= d.first <= d.n_windows - N, f"first {d.first}, n {N}: the rows are not inside 0 .. n_windows-1")
+    need(d.divisor != 0 and d.divisor == d.divisor, "divisor is 0 or NaN")
+    if n == "B":
+        need(d.max_invalid >= 0, "negative max_invalid")
+        need(d.pool_elems >= 0 and d.prefix_elems >= 0, "negative pool_elems or prefix_elems")
+    return T, N
+
+
+def table_rows(ptr, S, k=0):
+    """table k of [..][S][COLS] tables as lists of Python ints"""
+    return [[int(v) for v in row] for row in _i64(ptr, (k + 1) * S * COLS)[k * S * COLS:].reshape(S, COLS)]
+
+
+def check_sides(rows, scenes=None):
+    for s in (range(len(rows)) if scenes is None else scenes):
+        need(0 < rows[s][1] < 2 ** 31 and 0 < rows[s][2] < 2 ** 31, f"scene {s} has an extent outside 1 .. 2^31-1")
+
+
+def check_cum(rows, side):
+    """the checks of one host table for windows of ``side`` -> its total"""
+    total = 0
+    for s, (off, H, W, cum, poff) in enumerate(rows):
+        check_sides(rows, [s])
+        if H >= side and W >= side:
+            total += (H - side + 1) * (W - side + 1)
+        need(total < 2 ** 62, "the pool has 2^62 windows or more")
+        need(cum == total, f"cum_windows of scene {s} is not the running window count for tile {side}")
+    return total
+
+
+def check_extents(d, rows, with_prefix=True):
+    for s, (off, H, W, cum, poff) in enumerate(rows):
+        need(off >= 0 and off + d.C * H * W <= d.pool_elems, f"scene {s} lies outside the pool")
+        if with_prefix and poff >= 0:
+            need(d.prefix, f"scene {s} names a prefix table but prefix is null")
+            need(poff + (H + 1) * (W + 1) <= d.prefix_elems, f"the prefix table of scene {s} lies outside prefix_elems")
+
+
+def prefixes_of(d, table):
+    """per scene of the device table its prefix table or None; None without ``prefix``"""
+    if not d.prefix:
+        return None
+    allp = arr(d.prefix, d.prefix_elems, np.int32)
+    return [allp[r[4]:r[4] + (r[1] + 1) * (r[2] + 1)].reshape(r[1] + 1, r[2] + 1) if r[4] >= 0 else None for r in table]
+
+
+def deliver(d, table, rows, cutter):
+    """rgb, nir and coords of the window rows (s, y0, x0, word) from the scenes of the device table; ``cutter(scene, bands, y0, x0, T,
+    f, view, divisor)`` -> float32 [4][T][T]"""
+    T, n = d.tile, len(rows)
+    pool = _pool(d.pool, d.pool_elems, d.dtype)
+    rgb, nir = arr(d.rgb, n * 3 * T * T).reshape(n, 3, T, T), arr(d.nir, n * T * T).reshape(n, 1, T, T)
+    geo = arr(d.geo, d.S * 4, np.float64).reshape(d.S, 4) if d.geo else None
+    coords = arr(d.coords, n * 2).reshape(n, 2) if (d.coords and geo is not None) else None
+    for i, (s, y0, x0, word) in enumerate(rows):
+        off, H, W = table[s][:3]
+        f = (((word & 0xFFFFFFFF) >> 16) & 7) + 1
+        out = cutter(pool[off:off + d.C * H * W].reshape(d.C, H, W), d.band, y0, x0, T, f, word & 7, d.divisor)
+        rgb[i], nir[i, 0] = out[:3], out[3]
+        if coords is not None:
+            coords[i] = centre(geo[s], y0, x0, f * T)
+
+
+def deliver_drawn(d, table, win, cutter):
+    """the window words of a draw ``win`` (int64 [B][4]) and their batch"""
+    arr(d.window, d.B * 4, np.int32).reshape(d.B, 4)[...] = win.astype(np.uint32).view(np.int32).reshape(d.B, 4)
+    deliver(d, table, win.tolist(), cutter)
+
+
 class EmuScenePool(EmuClassMetrics):
-    def nirgan_scene_invalid_prefix(self, ref, stream=None):
-        who = "scene_invalid_prefix"
-        self.calls.append(who)
-        if not ref:
-            return self._fail(f"{who}: null pointer")
-        d = obj(ref)
-        if not d.pool or not d.prefix:
-            return self._fail(f"{who}: null pointer")
-        if d.dtype not in (0, 1):
-            return self._fail(f"{who}: unknown dtype")
-        if d.C <= 0 or d.H <= 0 or d.W <= 0:
-            return self._fail(f"{who}: bad shape")
-        if (d.H + 1) * (d.W + 1) >= 2 ** 31:
-            return self._fail(f"{who}: the table (H+1)(W+1) is 2^31 or more")
-        if any(not 0 <= b < d.C for b in d.band):
-            return self._fail(f"{who}: band outside 0 .. C-1")
-        if d.offset < 0 or d.pool_elems < 0 or d.offset + d.C * d.H * d.W > d.pool_elems:
-            return self._fail(f"{who}: the scene lies outside the pool")
-        if d.dtype == 0 and not 0 <= d.nodata <= 65535:
-            return self._fail(f"{who}: nodata outside 0 .. 65535")
+    @entry("scene_invalid_prefix")
+    def nirgan_scene_invalid_prefix(self, d):
+        need(d.pool and d.prefix, "null pointer")
+        need(d.dtype in (0, 1), "unknown dtype")
+        need(d.C > 0 and d.H > 0 and d.W > 0, "bad shape")
+        need((d.H + 1) * (d.W + 1) < 2 ** 31, "the table (H+1)(W+1) is 2^31 or more")
+        need(all(0 <= b < d.C for b in d.band), "band outside 0 .. C-1")
+        need(d.offset >= 0 and d.pool_elems >= 0 and d.offset + d.C * d.H * d.W <= d.pool_elems, "the scene lies outside the pool")
+        need(d.dtype != 0 or 0 <= d.nodata <= 65535, "nodata outside 0 .. 65535")
         scene = _pool(d.pool, d.pool_elems, d.dtype)[d.offset:d.offset + d.C * d.H * d.W].reshape(d.C, d.H, d.W)
         out = arr(d.prefix, (d.H + 1) * (d.W + 1), np.int32).reshape(d.H + 1, d.W + 1)
         out[...] = prefix_table(invalid_mask(scene[list(d.band)], d.nodata))
-        return 0
 
-    def nirgan_scene_sample(self, ref, stream=None):
-        who = "scene_sample"
-        self.calls.append(who)
-        if not ref:
-            return self._fail(f"{who}: null pointer")
-        d = obj(ref)
-        if not (d.pool and d.table and d.table_host and d.rgb and d.nir and d.window):
-            return self._fail(f"{who}: null pointer")
-        if d.dtype not in (0, 1):
-            return self._fail(f"{who}: unknown dtype")
-        if d.S <= 0 or d.C < 4:
-            return self._fail(f"{who}: bad pool (C must be at least 4)")
-        if d.views not in (1, 4, 8):
-            return self._fail(f"{who}: views {d.views} is not 1, 4 or 8")
-        if any(not 0 <= b < d.C for b in d.band):
-            return self._fail(f"{who}: band outside 0 .. C-1")
-        T, B = d.tile, d.B
-        if B <= 0 or T <= 0 or T * T >= 2 ** 31 or B * T * T >= 2 ** 31:
-            return self._fail(f"{who}: B, tile or B*tile*tile is not in 1 .. 2^31-1")
-        if d.divisor == 0 or d.divisor != d.divisor:
-            return self._fail(f"{who}: divisor is 0 or NaN")
-        if d.max_invalid < 0:
-            return self._fail(f"{who}: negative max_invalid")
-        if d.pool_elems < 0 or d.prefix_elems < 0:
-            return self._fail(f"{who}: negative pool_elems or prefix_elems")
-        host = [[int(v) for v in row] for row in _i64(d.table_host, d.S * COLS).reshape(d.S, COLS)]
-        total = 0
-        for s, (off, H, W, cum, poff) in enumerate(host):
-            if not (0 < H < 2 ** 31 and 0 < W < 2 ** 31):
-                return self._fail(f"{who}: scene {s} has an extent outside 1 .. 2^31-1")
-            if H >= T and W >= T:
-                total += (H - T + 1) * (W - T + 1)
-            if total >= 2 ** 62:
-                return self._fail(f"{who}: the pool has 2^62 windows or more")
-            if cum != total:
-                return self._fail(f"{who}: cum_windows of scene {s} is not the running window count for tile {T}")
-        if total == 0:
-            return self._fail(f"{who}: no scene holds a window of tile {T}")
-        for s, (off, H, W, cum, poff) in enumerate(host):
-            if off < 0 or off + d.C * H * W > d.pool_elems:
-                return self._fail(f"{who}: scene {s} lies outside the pool")
-            if poff >= 0:
-                if not d.prefix:
-                    return self._fail(f"{who}: scene {s} names a prefix table but prefix is null")
-                if poff + (H + 1) * (W + 1) > d.prefix_elems:
-                    return self._fail(f"{who}: the prefix table of scene {s} lies outside prefix_elems")
-        table = [[int(v) for v in row] for row in _i64(d.table, d.S * COLS).reshape(d.S, COLS)]     # the "device" copy
-        pool = _pool(d.pool, d.pool_elems, d.dtype)
-        shapes = [(r[1], r[2]) for r in table]
-        prefixes = None
-        if d.prefix:
-            allp = arr(d.prefix, d.prefix_elems, np.int32)
-            prefixes = [allp[r[4]:r[4] + (r[1] + 1) * (r[2] + 1)].reshape(r[1] + 1, r[2] + 1) if r[4] >= 0 else None for r in table]
-        win = draw_windows(shapes, T, B, d.views, (d.seed_lo, d.seed_hi), int(d.draw), int(d.sample0), prefixes, d.max_invalid)
-        arr(d.window, B * 4, np.int32).reshape(B, 4)[...] = win.astype(np.uint32).view(np.int32).reshape(B, 4)
-        rgb, nir = arr(d.rgb, B * 3 * T * T).reshape(B, 3, T, T), arr(d.nir, B * T * T).reshape(B, 1, T, T)
-        geo = arr(d.geo, d.S * 4, np.float64).reshape(d.S, 4) if d.geo else None
-        coords = arr(d.coords, B * 2).reshape(B, 2) if (d.coords and geo is not None) else None
-        for b, (s, y0, x0, word) in enumerate(win.tolist()):
-            off, H, W = table[s][:3]
-            scene = pool[off:off + d.C * H * W].reshape(d.C, H, W)
-            out = cut(scene, d.band, y0, x0, T, word & 7, d.divisor)
-            rgb[b], nir[b, 0] = out[:3], out[3]
-            if coords is not None:
-                coords[b] = centre(geo[s], y0, x0, T)
-        return 0
+    @entry("scene_sample")
+    def nirgan_scene_sample(self, d):
+        T, B = check_common(d)
+        host = table_rows(d.table_host, d.S)
+        need(check_cum(host, T) > 0, f"no scene holds a window of tile {T}")
+        check_extents(d, host)
+        table = table_rows(d.table, d.S)                                         # the "device" copy
+        win = draw_windows([(r[1], r[2]) for r in table], T, B, d.views, (d.seed_lo, d.seed_hi), int(d.draw), int(d.sample0),
+                           prefixes_of(d, table), d.max_invalid)
+        deliver_drawn(d, table, win, lambda scene, bands, y0, x0, T, f, view, divisor: cut(scene, bands, y0, x0, T, view, divisor))

@@ -128,6 +128,26 @@ def workload_width_small(dev):
     assert any(v & 4 for v in views) and any(not v & 4 for v in views), views    # both paths of the gather ran
 
 
+SEED_8_VIEWS = 0x5EEDC0DE12345693                                                # the 9 samples of draw 0 take all 8 views between them
+PARTIAL_TILES = (65, 70)
+
+
+def partial_second_block(dev, kind, T):
+    """one 4 x 150 x 131 scene, tile 65 or 70, B = 9, d4: the second 64-block of the gather is partial along the rows AND along the
+    columns (1 or 6 of 64), in the plain views and in the transposing ones -- all 8 occur in the one draw.  rgb, nir, coords and window
+    bitwise against the restatement, outputs guarded; the float32 scene holds NaN, which passes through like any value."""
+    rng = np.random.default_rng(65)
+    scene = rng.integers(0, 65536, size=(4, 150, 131), dtype=np.uint16)
+    if kind == "f32":
+        scene = scene.astype(np.float32)
+        scene[rng.random(scene.shape) < 0.01] = np.nan
+    geo = [GEO3[1]]
+    pool = ScenePool([scene], bands=(2, 1, 0, 3), divisor=10000.0 if kind == "u16" else 1.0, geotransforms=geo, device=dev)
+    want = check_batch(dev, pool, [scene], T, 9, "d4", SEED_8_VIEWS, 0, geo=geo)
+    assert set((want["window"][:, 3] & 7).tolist()) == set(range(8))
+    assert kind == "u16" or np.isnan(want["rgb"]).any()
+
+
 def small_scenes_are_never_chosen(dev):
     """tile 6: the 5 x 5 scene holds no window and is never drawn; tile 14: nothing holds one and the call raises"""
     import pytest

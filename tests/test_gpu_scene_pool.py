@@ -22,6 +22,12 @@ def test_workload_width_small():
     Sc.workload_width_small(DEV)
 
 
+@pytest.mark.parametrize("T", Sc.PARTIAL_TILES)
+@pytest.mark.parametrize("kind", ["u16", "f32"])
+def test_partial_second_block(kind, T):
+    Sc.partial_second_block(DEV, kind, T)
+
+
 def test_small_scenes_are_never_chosen():
     Sc.small_scenes_are_never_chosen(DEV)
 

@@ -35,6 +35,12 @@ def test_workload_width_small(emu):
     Sc.workload_width_small("cpu")
 
 
+@pytest.mark.parametrize("T", Sc.PARTIAL_TILES)
+@pytest.mark.parametrize("kind", ["u16", "f32"])
+def test_partial_second_block(emu, kind, T):
+    Sc.partial_second_block("cpu", kind, T)
+
+
 def test_small_scenes_are_never_chosen(emu):
     Sc.small_scenes_are_never_chosen("cpu")
 
