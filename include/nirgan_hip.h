@@ -445,6 +445,35 @@ typedef struct {
 #define NIRGAN_PIX_LOSS_WS_ELEMS 8192
 int nirgan_pix_loss(const nirgan_pix_loss_desc* d, void* stream);
 
+/* The same losses over the pixels a mask keeps (csrc/losses_masked.hip; the mask of a scene-pool batch is nirgan_scene_valid's, the
+ * last section of this header).  Every field up to ws_elems is nirgan_pix_loss_desc's, with the same meaning and the same checks.
+ *   valid  float [B][1][H][W], device.  A pixel i takes part iff valid[i] != 0.f (-0.f drops it; any other value, NaN included, keeps it).
+ *   count  int32 [1], DEVICE memory, read by the kernel: the divisor of the mean, normally nirgan_valid_count of `valid` -- or of the
+ *          mask of a larger batch this call is one part of, whose parts then share one divisor.  Nothing is read back to the host.
+ * Per kept pixel the arithmetic is nirgan_pix_loss's, operation for operation, with
+ *     inv = count[0] > 0 ? 1.f / (float)count[0] : 0.f        in the place of 1.f / (float)n.
+ * A dropped pixel adds nothing to any of the seven sums, and grad_pred there is exactly extra_scale * extra[...][extra_c], or +0.0f
+ * without `extra`.  Its rgb, nir and pred are NOT LOADED: NaN, Inf or nodata / divisor at a dropped pixel reach no output.
+ * Same grid, same per-block partial sums in `ws`, same fixed-order finish: with valid all ones and count[0] = n the sums and the
+ * gradient are BITWISE those of nirgan_pix_loss.  With count[0] <= 0 the sums still accumulate over the kept pixels and the loss
+ * part of the gradient is 0.  The caller divides the sums by the count.
+ * Everything nirgan_pix_loss refuses, and a NULL valid or count, return NIRGAN_ERR_ARG before any launch. */
+typedef struct {
+    const float* rgb;
+    const float* nir; const float* pred;
+    int B, H, W;
+    float w_l1, w_ndvi, w_ndwi, w_gndvi, w_savi, w_msavi, w_evi;
+    int criterion;
+    int log_all;
+    const float* extra; int extra_cs, extra_c; float extra_scale;
+    float* sums;
+    float* grad_pred;
+    float* ws; int64_t ws_elems;
+    const float* valid;                   /* [B][1][H][W] */
+    const int32_t* count;                 /* device [1] */
+} nirgan_pix_loss_masked_desc;
+int nirgan_pix_loss_masked(const nirgan_pix_loss_masked_desc* d, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Per-pixel baseline models, fused (csrc/pixmlp.hip).  rgb [B][3][H][W], nir / pred / dpred [B][1][H][W], fp32 NCHW, contiguous.
  *   hidden = 0   Linear_NIR: y = w . x + b                                    model/baseline_models.py:17-30
@@ -1474,6 +1503,54 @@ typedef struct {
 int nirgan_scene_tile_invalid(const nirgan_scene_predict_desc* d, void* stream);
 int nirgan_scene_tile_gather(const nirgan_scene_predict_desc* d, void* stream);
 int nirgan_scene_finish(const nirgan_scene_predict_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Valid-pixel masks of scene-pool windows: the third place nodata is handled.  A sampler accepts a window with up to max_invalid
+ * invalid pixels and delivers them as ordinary values; nirgan_scene_valid gives, for the same window rows, which pixels of the
+ * DELIVERED tile are clean, and nirgan_pix_loss_masked (above) keeps the others out of the generator's reconstruction losses.
+ *
+ * nirgan_scene_valid: ONE launch, no atomics, no host synchronisation.
+ * table / table_host: int64 [S][NIRGAN_SCENE_TABLE_COLS] in the format of nirgan_scene_sample; columns 1, 2 and 4 (H_s, W_s, prefix
+ * offset) are read, column 0 is carried by the table but not used (no pixel is read), column 3 (cum_windows) is IGNORED: the table
+ * of any tile size will do.  prefix / prefix_elems: the scenes' invalid-prefix tables (nirgan_scene_invalid_prefix), or NULL.
+ * window / window_host, n_windows, first, n, tile: as in nirgan_scene_gather_desc.  A row is { s, y0, x0, word }, parsed as there:
+ *     view = word & 7;   f = ((word >> 16) & 7) + 1;   L = f * T;   y0, x0 in SOURCE pixels
+ * With P the prefix table of scene s, [(H_s+1)][(W_s+1)]:
+ *     c(p, q)  = P[y0+(p+1)f][x0+(q+1)f] - P[y0+pf][x0+(q+1)f] - P[y0+(p+1)f][x0+qf] + P[y0+pf][x0+qf]      (int32, exact)
+ *     D[p][q]  = c(p, q) == 0 ? 1.0f : 0.0f                     the f x f source block of delivered pixel (p, q) holds no invalid pixel
+ *     valid[i][0][j1][j2] = D[j1'][j2']
+ * with (j1', j2') by the view rule of nirgan_tile_views_expand on the T x T tile: the mask has the orientation of the pixels that
+ * either sampler, or nirgan_scene_gather, delivered for the same row.  A scene without a table (table[s][4] < 0), or prefix == NULL,
+ * gives all ones.  A float pool's table counts NaN pixels, so the same rule serves it.  valid is float [n][1][T][T]; every element
+ * is written by one thread, the output needs no initialisation, nothing outside it is written.
+ *
+ * window_host may be NULL: the rows were just written by a draw on the same stream and no host copy exists.  The kernel then bounds
+ * every row itself: a row with s outside 0 .. S-1, y0 < 0, x0 < 0, y0 + L > H_s or x0 + L > W_s gives an ALL-ZERO tile and nothing of
+ * the prefix tables is read for it; the other rows are unaffected.  (The kernel makes this check for every call.)  With window_host
+ * set, such a row -- and a stray bit in its word, and (f*T)^2 at 2^31 or more -- is refused on the host as nirgan_scene_gather refuses
+ * it, before any launch, the message naming the row.
+ * Argument errors return NIRGAN_ERR_ARG before any launch: a null pointer (d, table, table_host, window, valid); S <= 0; tile, n or
+ * n*tile*tile outside 1 .. 2^31-1; first < 0 or first + n > n_windows; negative prefix_elems; a table row with an extent outside
+ * 1 .. 2^31-1; with prefix set, a prefix table outside prefix_elems.
+ *
+ * nirgan_valid_count: count[0] (int32, device, OVERWRITTEN) = the number of i < n with valid[i] != 0.f (-0.f is not counted; a
+ * denormal, any other value and NaN are).  Integer sums: exact and independent of scheduling.  A 4-byte clear and one launch on the
+ * stream.  n outside 1 .. 2^31-1 or a null pointer return NIRGAN_ERR_ARG before either.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    int S;
+    const int64_t* table;                 /* device [S][NIRGAN_SCENE_TABLE_COLS]; columns 1, 2 and 4 are read */
+    const int64_t* table_host;            /* the same table in HOST memory: every check reads it */
+    const int32_t* prefix; int64_t prefix_elems;   /* device, or NULL: all ones */
+    int tile;                             /* side T of the DELIVERED tile */
+    const int32_t* window;                /* device [n_windows][4] */
+    const int32_t* window_host;           /* the same words in HOST memory, or NULL: the kernel bounds the rows */
+    int64_t n_windows;
+    int64_t first; int n;                 /* rows [first, first + n) */
+    float* valid;                         /* [n][1][T][T], OVERWRITTEN */
+} nirgan_scene_valid_desc;
+int nirgan_scene_valid(const nirgan_scene_valid_desc* d, void* stream);
+int nirgan_valid_count(const float* valid, int64_t n, int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -45,12 +45,17 @@ def _cfg(node, name, default=None):
 class HipL1Loss(torch.nn.Module):
     """torch.nn.L1Loss() for (prediction, target) NIR tiles on the fused HIP pixel-loss pass."""
 
-    def forward(self, pred, target):
+    def forward(self, pred, target, valid=None):
+        """``valid``: a [B,1,H,W] mask (``valid != 0``, shared by the channels): the mean runs over its pixels only, 0 if there is none"""
         if pred.dim() != 4 or pred.shape != target.shape:
             raise ValueError(f"HipL1Loss: prediction {tuple(pred.shape)} and target {tuple(target.shape)} must be equal 4-d shapes")
         B, C, H, W = pred.shape
+        if valid is not None:
+            if tuple(valid.shape) != (B, 1, H, W):
+                raise ValueError(f"HipL1Loss: valid {tuple(valid.shape)} must be {(B, 1, H, W)}")
+            valid = valid.expand(B, C, H, W).reshape(B * C, 1, H, W)
         # the mean over all elements does not care how they are split over (B, C): any channel count runs as B*C planes
-        return HF.PixLossFn.apply(None, target.reshape(B * C, 1, H, W), pred.reshape(B * C, 1, H, W), (1.0, 0, 0, 0, 0, 0, 0), 0)
+        return HF.pix_loss(None, target.reshape(B * C, 1, H, W), pred.reshape(B * C, 1, H, W), (1.0, 0, 0, 0, 0, 0, 0), 0, valid)
 
 
 class Px2Px_PL(_Base):
@@ -155,17 +160,20 @@ class Px2Px_PL(_Base):
             pred_fake = self.netD(fake_AB)
             loss_G_GAN = self.criterionGAN(pred_fake, True)
             self._log("model_loss/generator_GAN_loss", loss_G_GAN)
-            loss_G_L1 = self.criterionL1(pred, nir)
+            valid = batch.get("valid")                                   # the loader's mask (return_valid=True): the reconstruction terms skip nodata
+            loss_G_L1 = self.criterionL1(pred, nir, valid)
             self._log("model_loss/generator_L1", loss_G_L1)
             loss_G = loss_G_GAN * self.opt.lambda_GAN + loss_G_L1 * self.opt.lambda_L1
             if self.lambda_ssim > 0.0:                                   # pix2pix.py:233-237
+                if valid is not None:
+                    raise NotImplementedError("valid with lambda_ssim > 0: the SSIM windows would straddle the mask")
                 from utils.losses import ssim_loss
                 loss_G_ssim = ssim_loss(pred, nir)
                 self._log("model_loss/generator_ssim", loss_G_ssim)
                 loss_G = loss_G + loss_G_ssim * self.lambda_ssim
             if self.opt.lambda_rs_losses > 0.0:
                 losses_rs_indices = self.rs_losses.get_and_weight_losses(rgb, nir, pred,
-                                                                         loss_config=dict(self.opt.internal_rs_loss_weights))
+                                                                         loss_config=dict(self.opt.internal_rs_loss_weights), valid=valid)
                 self._log("model_loss/indices_loss_weighted", losses_rs_indices)
                 loss_G = loss_G + losses_rs_indices * self.opt.lambda_rs_losses
             self._log("model_loss/generator_total_loss", loss_G)
@@ -293,4 +301,4 @@ class Px2Px_PL(_Base):
             (rgb, nir), embeds = self.extract_batch(batch), None
         tr = self.fused_trainer()
         tr.real_label, tr.fake_label = self.criterionGAN._label_value(True), self.criterionGAN._label_value(False)   # networks.py:229-230
-        return tr.step(rgb, nir, embeds)
+        return tr.step(rgb, nir, embeds, valid=batch.get("valid"))

@@ -36,6 +36,13 @@ held-out rectangle (widened by ``guard`` pixels), whatever the nodata attempts d
 ``pool.predict(model, s, ...)`` is the inference side: the NIR band of scene ``s`` through ``nirgan_hip.inference.predict_scene``,
 read in place from the pool's buffer.
 
+With ``max_invalid > 0`` a window is delivered with its nodata pixels as ordinary values.  ``return_valid=True`` (``sample``,
+``loader``, ``gather``, ``grid_loader``, on the pool and on both halves of a split) adds ``"valid"`` [B,1,T,T] to the batch: 1 where the
+pixel's source block is clean, from the prefix tables in one ``nirgan_scene_valid`` launch.  ``train_batch`` /
+``Pix2PixTrainer.step(..., valid=)`` then keep the other pixels out of L1 and the index losses:
+
+    fit(model, pool.loader(16, 256, steps_per_epoch=1000, seed=1, max_invalid=256 * 256 // 2, return_valid=True), max_epochs=10)
+
 Reading ``.tif`` is out of scope (no rasterio here): convert once to ``.npz``.
 """
 from __future__ import annotations
@@ -95,6 +102,28 @@ def _fill(d, pool, table, out, tile, draw=None):
         d.window = out["window"].data_ptr()
 
 
+def _valid_out(pool, out, n, tile):
+    """``out["valid"]``, a contiguous float32 [n, 1, T, T] tensor on the pool's device, made if ``out`` holds none"""
+    t = out.get("valid")
+    if t is None:
+        t = out["valid"] = torch.empty((n, 1, tile, tile), dtype=torch.float32, device=pool.device)
+    if tuple(t.shape) != (n, 1, tile, tile) or t.dtype != torch.float32 or t.device != pool.pool.device or not t.is_contiguous():
+        raise ValueError(f"out['valid'] must be a contiguous float32 {(n, 1, tile, tile)} tensor on {pool.pool.device}")
+    return t
+
+
+def _scene_valid(pool, tile, window, window_host, n_windows, first, n, valid):
+    """One ``nirgan_scene_valid`` launch: the mask of rows ``first .. first + n - 1`` of the device rows ``window`` into
+    ``valid``.  ``window_host``: the same rows as a numpy array, or None -- the rows of a draw, which the kernel bounds itself."""
+    d = L.SceneValidDesc()
+    table = pool._table(tile)                                                    # columns 1, 2, 4 are read: the table of any side will do
+    d.S, d.table, d.table_host = len(pool.shapes), table[0].data_ptr(), table[1].ctypes.data
+    d.prefix, d.prefix_elems = (pool.prefix.data_ptr() if pool.prefix is not None else None), pool.prefix_elems
+    d.tile, d.window, d.window_host = tile, window.data_ptr(), (window_host.ctypes.data if window_host is not None else None)
+    d.n_windows, d.first, d.n, d.valid = n_windows, first, n, valid.data_ptr()
+    L.call("nirgan_scene_valid", C.byref(d), _stream(pool.device))
+
+
 def _fill_scales(d, factors, weights):
     d.K = len(factors)
     d.factor, d.weight = (C.c_int * 8)(*factors), (C.c_uint32 * 8)(*weights)
@@ -105,7 +134,7 @@ class _Sampler:
     ``_outputs`` and names its entry and descriptor in ``_describe``."""
 
     def sample(self, batch_size, tile, *, seed, draw, sample0=0, augment="d4", max_invalid=0, return_windows=False, out=None,
-               scales=None, scale_weights=None):
+               scales=None, scale_weights=None, return_valid=False):
         """One batch ``{"rgb" [B,3,T,T], "nir" [B,1,T,T][, "coords" [B,2]]}``, plus ``"window"`` [B,4] int32 = (scene, y0, x0,
         view | attempt << 8 | (factor - 1) << 16 | exhausted << 31) with ``return_windows``.  Sample b is a function of ``(seed, draw,
         sample0 + b)`` alone.  ``augment``: "d4" (8 views), "flips" (4) or "none".  ``max_invalid``: the most invalid pixels a window
@@ -114,7 +143,11 @@ class _Sampler:
         ``scales``: distinct resolution factors in 1 .. 8 (sorted before use), one drawn per sample with the positive integer
         ``scale_weights`` (default: all 1); the sample is then an f*T window of the source (y0, x0 in source pixels, ``max_invalid``
         per f x f block, coords of the window's centre) delivered as the T x T tile of its f x f block means.  None: factor 1 -- a
-        ``ScenePool`` through ``nirgan_scene_sample``, as ever; a ``SplitTrain`` through its one entry."""
+        ``ScenePool`` through ``nirgan_scene_sample``, as ever; a ``SplitTrain`` through its one entry.
+        ``return_valid``: the batch also carries ``"valid"`` [B,1,T,T] float32, 1 where the pixel's f x f source block holds no invalid
+        pixel and 0 elsewhere, in the orientation of the delivered pixels (all ones without ``nodata``): one ``nirgan_scene_valid``
+        launch on the rows the draw just wrote, no copy to the host.  ``Pix2PixTrainer.step(..., valid=)`` and the
+        losses' ``valid=`` take it."""
         if augment not in L.SCENE_VIEWS:
             raise ValueError(f"augment must be one of {sorted(L.SCENE_VIEWS)}, got {augment!r}")
         B, tile = int(batch_size), int(tile)
@@ -122,14 +155,20 @@ class _Sampler:
             raise ValueError("batch_size and tile must be positive")
         out = out if out is not None else self._outputs(B, tile)
         entry, d = self._describe(out, B, tile, seed, draw, sample0, augment, max_invalid, scales, scale_weights)
+        pool = self if isinstance(self, ScenePool) else self.pool               # the ScenePool itself, or a SplitTrain's
+        if return_valid:
+            valid = _valid_out(pool, out, B, tile)
         L.call(entry, C.byref(d), _stream(self.device))
-        return out if return_windows else {k: v for k, v in out.items() if k != "window"}
+        if return_valid:
+            _scene_valid(pool, tile, out["window"], None, B, 0, B, valid)
+        drop = [k for k, keep in (("window", return_windows), ("valid", return_valid)) if not keep and k in out]
+        return {k: v for k, v in out.items() if k not in drop} if drop else out
 
     def loader(self, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
-               scale_weights=None):
+               scale_weights=None, return_valid=False):
         """``SceneLoader`` over this source: it only asks for ``_outputs`` and ``sample``"""
         return SceneLoader(self, batch_size, tile, steps_per_epoch, seed=seed, augment=augment, max_invalid=max_invalid, rank=rank,
-                           world=world, scales=scales, scale_weights=scale_weights)
+                           world=world, scales=scales, scale_weights=scale_weights, return_valid=return_valid)
 
 
 def _grid(pool, regions, tile, factors, stride, max_invalid, cover, nothing_left):
@@ -169,13 +208,13 @@ def _grid(pool, regions, tile, factors, stride, max_invalid, cover, nothing_left
     return WindowList(rows, pool.device)
 
 
-def _grid_loader(pool, grid, batch_size, tile, rank, world, **kw):
+def _grid_loader(pool, grid, batch_size, tile, rank, world, return_valid=False, **kw):
     """``GridLoader`` over this rank's rows of ``grid(tile, **kw)``: the rows i with ``i % world == rank``, in order"""
     if not 0 <= int(rank) < int(world):
         raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
     full = grid(tile, **kw)
     mine = full if int(world) == 1 else WindowList(full.host[int(rank)::int(world)], pool.device)
-    return GridLoader(pool, mine, batch_size, tile)
+    return GridLoader(pool, mine, batch_size, tile, return_valid=return_valid)
 
 
 class ScenePool(_Sampler):
@@ -342,14 +381,15 @@ class ScenePool(_Sampler):
             return [(s, 0, 0) + self.shapes[s] for s in ids]
         return _grid(self, regions, tile, factors, stride, max_invalid, cover, "is left on these scenes")
 
-    def gather(self, windows, tile, *, first=0, count=None, out=None):
+    def gather(self, windows, tile, *, first=0, count=None, out=None, return_valid=False):
         """``{"rgb" [n,3,T,T], "nir" [n,1,T,T][, "coords" [n,2]]}`` of the rows ``first .. first + count - 1`` (default: to the end) of
         an explicit list of windows, through ``nirgan_scene_gather``: bitwise what ``sample`` delivered for the same window rows.
         ``windows``: a ``WindowList`` (of ``grid``), or any int32 tensor or array [n, 4] of (scene, y0, x0, word) rows such as the
         ``"window"`` of ``sample(..., return_windows=True)``; an array or tensor is wrapped in a ``WindowList`` on every call, which
         costs a tensor on the device one copy to the host (a synchronisation) -- wrap it once yourself to cut it repeatedly.
         ``tile``: the side T of the delivered tiles; a row of factor f cuts f*T source pixels.  ``out``: the dict of tensors to write
-        into (same shapes) instead of new ones."""
+        into (same shapes) instead of new ones.  ``return_valid``: also ``"valid"`` [n,1,T,T], the mask of ``sample(...,
+        return_valid=True)`` for the same rows, bitwise; the rows' host copy is checked as the gather checks it."""
         if self.device.type != "cuda" and not L.is_emulated():
             raise RuntimeError("ScenePool.gather: the pool must live on the MI355X (cuda); the HIP path has no CPU fallback")
         wl = windows if isinstance(windows, WindowList) else WindowList(windows, self.device)
@@ -368,14 +408,20 @@ class ScenePool(_Sampler):
         d = L.SceneGatherDesc()
         _fill(d, self, self._table(tile), out, tile)                             # columns 0 .. 2 are read: the table of any side will do
         d.window, d.window_host, d.n_windows, d.first, d.n = wl.device.data_ptr(), wl.host.ctypes.data, len(wl), first, n
+        if return_valid:
+            valid = _valid_out(self, out, n, tile)
         L.call("nirgan_scene_gather", C.byref(d), _stream(self.device))
-        return {k: out[k] for k in ("rgb", "nir", "coords") if k in out and (k != "coords" or self.geo is not None)}
+        if return_valid:
+            _scene_valid(self, tile, wl.device, wl.host, len(wl), first, n, valid)
+        keys = ("rgb", "nir", "coords") + (("valid",) if return_valid else ())
+        return {k: out[k] for k in keys if k in out and (k != "coords" or self.geo is not None)}
 
-    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None, rank=0, world=1):
+    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, scenes=None, rank=0, world=1,
+                    return_valid=False):
         """``GridLoader`` over ``grid(tile, ...)``: a fixed validation set.  Rank ``rank`` of ``world`` takes the rows i of the grid
         with ``i % world == rank``, in order."""
-        return _grid_loader(self, self.grid, batch_size, tile, rank, world, factors=factors, stride=stride, max_invalid=max_invalid,
-                            cover=cover, scenes=scenes)
+        return _grid_loader(self, self.grid, batch_size, tile, rank, world, return_valid, factors=factors, stride=stride,
+                            max_invalid=max_invalid, cover=cover, scenes=scenes)
 
     def scene(self, s: int) -> torch.Tensor:
         """Scene ``s`` as a [C, H, W] VIEW of the pool's buffer (int16 bit patterns of a uint16 pool); nothing is copied."""
@@ -607,14 +653,14 @@ class SplitVal:
         ValueError if no window is left."""
         return _grid(self.pool, lambda: self.split.rectangles, tile, factors, stride, max_invalid, cover, "lies inside a held-out rectangle")
 
-    def gather(self, windows, tile, *, first=0, count=None, out=None):
+    def gather(self, windows, tile, *, first=0, count=None, out=None, return_valid=False):
         """``ScenePool.gather``: the rows are cut as they are named, whichever half they came from"""
-        return self.pool.gather(windows, tile, first=first, count=count, out=out)
+        return self.pool.gather(windows, tile, first=first, count=count, out=out, return_valid=return_valid)
 
-    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, rank=0, world=1):
+    def grid_loader(self, batch_size, tile, *, factors=(1,), stride=None, max_invalid=0, cover=True, rank=0, world=1, return_valid=False):
         """``GridLoader`` over ``grid(tile, ...)``; rank ``rank`` of ``world`` takes the rows i with ``i % world == rank``, in order"""
-        return _grid_loader(self.pool, self.grid, batch_size, tile, rank, world, factors=factors, stride=stride, max_invalid=max_invalid,
-                            cover=cover)
+        return _grid_loader(self.pool, self.grid, batch_size, tile, rank, world, return_valid, factors=factors, stride=stride,
+                            max_invalid=max_invalid, cover=cover)
 
 
 def _grid_starts(extent, side, step, cover):
@@ -659,13 +705,14 @@ class GridLoader:
     than that back, so give it a ``batch_size`` no larger than the loader's.  ``windows``: this rank's rows; ``factor_of_row``:
     their resolution factors (numpy).  It has no ``__getitem__``: it is an iterable of batches, not a dataset of samples."""
 
-    def __init__(self, pool, windows, batch_size, tile):
+    def __init__(self, pool, windows, batch_size, tile, return_valid=False):
         if int(batch_size) <= 0 or int(tile) <= 0:
             raise ValueError("batch_size and tile must be positive")
         if not len(windows):
             raise ValueError("a GridLoader needs at least one window (this rank's share of the grid is empty)")
         self.pool, self.windows, self.batch_size, self.tile = pool, windows, int(batch_size), int(tile)
         self.factor_of_row = ScenePool.window_factor(windows.host)
+        self.return_valid = bool(return_valid)                                  # the batches carry "valid" (``ScenePool.gather``)
         self._buffers = None
 
     def __len__(self):
@@ -674,15 +721,18 @@ class GridLoader:
     def __iter__(self):
         if self._buffers is None:
             self._buffers = {k: v for k, v in self.pool._outputs(self.batch_size, self.tile).items() if k != "window"}
+            if self.return_valid:
+                _valid_out(self.pool, self._buffers, self.batch_size, self.tile)
         for first in range(0, len(self.windows), self.batch_size):
             n = min(self.batch_size, len(self.windows) - first)
-            yield self.pool.gather(self.windows, self.tile, first=first, count=n, out={k: v[:n] for k, v in self._buffers.items()})
+            yield self.pool.gather(self.windows, self.tile, first=first, count=n, out={k: v[:n] for k, v in self._buffers.items()},
+                                   return_valid=self.return_valid)
 
     def by_factor(self):
         """``(f, GridLoader)`` for every factor of the list in ascending order, each over the rows of that factor alone"""
         for f in sorted(set(self.factor_of_row.tolist())):
             yield f, GridLoader(self.pool, WindowList(self.windows.host[self.factor_of_row == f], self.windows.device.device),
-                                self.batch_size, self.tile)
+                                self.batch_size, self.tile, return_valid=self.return_valid)
 
 
 def check_scales(scales, scale_weights=None):
@@ -712,10 +762,11 @@ class SceneLoader:
     """A re-iterable of ``steps_per_epoch`` batches per epoch.  Step i of epoch e is ``pool.sample(..., draw=e * steps_per_epoch + i,
     sample0=rank * batch_size, scales=..., scale_weights=...)``.  ``set_epoch(e)`` names the epoch of the next ``iter()`` (``fit`` calls it, so a resumed run
     continues where the checkpoint stopped); without it every ``iter()`` moves on by one epoch.  The batches of one loader share their
-    tensors: a batch is valid until the next one is drawn, nothing is allocated per step."""
+    tensors: a batch is valid until the next one is drawn, nothing is allocated per step.  With ``return_valid`` every batch also carries
+    the mask ``"valid"`` of ``sample`` -- one more tensor of the loader's own, one more launch per batch."""
 
     def __init__(self, pool, batch_size, tile, steps_per_epoch, *, seed, augment="d4", max_invalid=0, rank=0, world=1, scales=None,
-                 scale_weights=None):
+                 scale_weights=None, return_valid=False):
         if not 0 <= int(rank) < int(world):
             raise ValueError(f"rank {rank} outside 0 .. world-1 = {int(world) - 1}")
         if int(steps_per_epoch) <= 0:
@@ -727,6 +778,7 @@ class SceneLoader:
         if scales is None and scale_weights is not None:
             raise ValueError("scale_weights without scales")
         self.scales, self.scale_weights = (None, None) if scales is None else check_scales(scales, scale_weights)
+        self.return_valid = bool(return_valid)                                  # the batches carry "valid" (``sample``)
         self.epoch = 0
         self._buffers = None                                                     # one set of output tensors, made at the first iter()
 
@@ -743,4 +795,5 @@ class SceneLoader:
         for i in range(self.steps_per_epoch):
             yield self.pool.sample(self.batch_size, self.tile, seed=self.seed, draw=epoch * self.steps_per_epoch + i,
                                    sample0=self.rank * self.batch_size, augment=self.augment, max_invalid=self.max_invalid,
-                                   out=self._buffers, scales=self.scales, scale_weights=self.scale_weights)
+                                   out=self._buffers, scales=self.scales, scale_weights=self.scale_weights,
+                                   return_valid=self.return_valid)

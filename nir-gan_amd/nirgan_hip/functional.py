@@ -242,9 +242,84 @@ class PixLossFn(torch.autograd.Function):
         return None, None, grad * gout, None, None
 
 
-def index_sums(rgb, nir, pred, criterion: int) -> torch.Tensor:
-    """All seven per-pixel criterion sums (L1 + six indices), forward only: the 'logging_dict' mode."""
+def as_valid(valid, like: torch.Tensor) -> torch.Tensor:
+    """A mask as the masked entries read it: contiguous float32 of ``like``'s shape on its device.  Any tensor of that shape is taken
+    as ``valid != 0``; a float32 one goes through as it is (the kernels make the same test)."""
+    if tuple(valid.shape) != tuple(like.shape):
+        raise ValueError(f"valid {tuple(valid.shape)} must have the shape of the prediction {tuple(like.shape)}")
+    v = valid.detach().to(like.device)
+    return (v if v.dtype == torch.float32 else (v != 0).float()).contiguous()
+
+
+def valid_count(valid: torch.Tensor) -> torch.Tensor:
+    """int32 [1] on the device: how many elements of the float32 mask are not 0 (``nirgan_valid_count``; exact, nothing is read back)"""
+    count = torch.empty(1, dtype=torch.int32, device=valid.device)
+    st = torch.cuda.current_stream(valid.device).cuda_stream if valid.device.type == "cuda" else None
+    L.call("nirgan_valid_count", valid.data_ptr(), valid.numel(), count.data_ptr(), st)
+    return count
+
+
+def _masked_desc(rgb_, nir_, pred_, valid_, count, sums, grad, criterion, log_all, ws):
+    d = L.PixLossMaskedDesc()
+    B, _, H, W = pred_.shape
+    d.rgb = None if rgb_ is None else rgb_.data_ptr()
+    d.nir, d.pred, d.B, d.H, d.W = nir_.data_ptr(), pred_.data_ptr(), B, H, W
+    d.criterion, d.log_all = criterion, log_all
+    d.sums, d.grad_pred = sums.data_ptr(), (None if grad is None else grad.data_ptr())
+    d.ws, d.ws_elems = ws.data_ptr(), ws.numel()
+    d.valid, d.count = valid_.data_ptr(), count.data_ptr()
+    return d
+
+
+class PixLossMaskedFn(torch.autograd.Function):
+    """``PixLossFn`` over the pixels with ``valid != 0``: one count, then ``nirgan_pix_loss_masked``.  The mean is over
+    the count; with no valid pixel the loss is 0 and so is the gradient.  Nothing is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, rgb, nir, pred, valid, weights: Tuple[float, ...], criterion: int):
+        _require_device(pred, "pixel losses")
+        nir_, pred_ = (t.detach().contiguous().float() for t in (nir, pred))
+        rgb_ = None if rgb is None else rgb.detach().contiguous().float()
+        valid_ = as_valid(valid, pred_)
+        count = valid_count(valid_)
+        sums = torch.zeros(8, dtype=torch.float32, device=pred_.device)
+        grad = torch.empty_like(pred_)
+        ws = torch.empty(L.PIX_LOSS_WS_ELEMS, dtype=torch.float32, device=pred_.device)
+        d = _masked_desc(rgb_, nir_, pred_, valid_, count, sums, grad, criterion, 0, ws)
+        (d.w_l1, d.w_ndvi, d.w_ndwi, d.w_gndvi, d.w_savi, d.w_msavi, d.w_evi) = [float(w) for w in weights]
+        st = torch.cuda.current_stream(pred_.device).cuda_stream if pred_.device.type == "cuda" else None
+        L.call("nirgan_pix_loss_masked", C.byref(d), st)
+        ctx.save_for_backward(grad)
+        w = torch.tensor(list(weights) + [0.0], dtype=torch.float32, device=pred_.device)
+        return (sums * w).sum() / count.clamp(min=1).float()[0]                  # count 0: every sum is 0
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grad,) = ctx.saved_tensors
+        return None, None, grad * gout, None, None, None
+
+
+def pix_loss(rgb, nir, pred, weights: Tuple[float, ...], criterion: int, valid=None):
+    """``PixLossFn``, or ``PixLossMaskedFn`` when a mask is given"""
+    if valid is None:
+        return PixLossFn.apply(rgb, nir, pred, weights, criterion)
+    return PixLossMaskedFn.apply(rgb, nir, pred, valid, weights, criterion)
+
+
+def index_sums(rgb, nir, pred, criterion: int, valid=None) -> torch.Tensor:
+    """All seven per-pixel criterion sums (L1 + six indices), forward only: the 'logging_dict' mode.  ``valid``: the means are over
+    the pixels with ``valid != 0`` (0 where there is none)."""
     _require_device(pred, "pixel losses")
+    if valid is not None:
+        rgb_, nir_, pred_ = (t.detach().contiguous().float() for t in (rgb, nir, pred))
+        valid_ = as_valid(valid, pred_)
+        count = valid_count(valid_)
+        sums = torch.zeros(8, dtype=torch.float32, device=pred_.device)
+        ws = torch.empty(L.PIX_LOSS_WS_ELEMS, dtype=torch.float32, device=pred_.device)
+        d = _masked_desc(rgb_, nir_, pred_, valid_, count, sums, None, criterion, 1, ws)
+        st = torch.cuda.current_stream(pred_.device).cuda_stream if pred_.device.type == "cuda" else None
+        L.call("nirgan_pix_loss_masked", C.byref(d), st)
+        return sums[:7] / count.clamp(min=1).float()[0]
     B, _, H, W = pred.shape
     rgb_, nir_, pred_ = (t.detach().contiguous().float() for t in (rgb, nir, pred))
     sums = torch.zeros(8, dtype=torch.float32, device=pred_.device)

@@ -96,6 +96,10 @@ class PixLossDesc(C.Structure):
                 ("sums", fp), ("grad_pred", fp), ("ws", fp), ("ws_elems", i64)]
 
 
+class PixLossMaskedDesc(C.Structure):
+    _fields_ = PixLossDesc._fields_ + [("valid", fp), ("count", fp)]
+
+
 PIXMLP_TILE = 32                # include/nirgan_hip.h: NIRGAN_PIXMLP_TILE
 
 
@@ -263,6 +267,11 @@ class SceneOriginsDesc(C.Structure):
     _fields_ = SceneScaledDesc._fields_ + [("origins", fp), ("origins_host", fp), ("R", i32), ("first", i32 * 8), ("count", i32 * 8)]
 
 
+class SceneValidDesc(C.Structure):
+    _fields_ = [("S", i32), ("table", fp), ("table_host", fp), ("prefix", fp), ("prefix_elems", i64), ("tile", i32), ("window", fp),
+                ("window_host", fp), ("n_windows", i64), ("first", i64), ("n", i32), ("valid", fp)]
+
+
 SCENE_OUT_U16, SCENE_OUT_F16, SCENE_OUT_F32 = 0, 1, 2     # include/nirgan_hip.h: NIRGAN_SCENE_OUT_*
 SCENE_OUT_KINDS = {"uint16": SCENE_OUT_U16, "float16": SCENE_OUT_F16, "float32": SCENE_OUT_F32}
 
@@ -342,6 +351,8 @@ PROTOTYPES = {
     "nirgan_scene_tile_invalid": (i32, [C.POINTER(ScenePredictDesc), fp]),
     "nirgan_scene_tile_gather": (i32, [C.POINTER(ScenePredictDesc), fp]),
     "nirgan_scene_finish": (i32, [C.POINTER(ScenePredictDesc), fp]),
+    "nirgan_scene_valid": (i32, [C.POINTER(SceneValidDesc), fp]),
+    "nirgan_valid_count": (i32, [fp, i64, fp, fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
     "nirgan_wino6_weights": (i32, [fp, i32, i32, i32, fp, fp]),
@@ -394,6 +405,7 @@ PROTOTYPES = {
     "nirgan_lsgan": (i32, [fp, i64, f32, f32, fp, fp, fp]),
     "nirgan_gan_loss": (i32, [fp, i64, i32, f32, f32, fp, fp, fp]),
     "nirgan_pix_loss": (i32, [C.POINTER(PixLossDesc), fp]),
+    "nirgan_pix_loss_masked": (i32, [C.POINTER(PixLossMaskedDesc), fp]),
     "nirgan_pixmlp_fwd": (i32, [C.POINTER(PixMlpDesc), fp]),
     "nirgan_pixmlp_train": (i32, [C.POINTER(PixMlpDesc), fp]),
     "nirgan_pixmlp_ws_elems": (i64, [i32, i32, i32, i32]),

@@ -18,6 +18,13 @@ reproduce ``pred`` bit for bit -- with dropout the reference's second forward dr
 mask; here both passes of a batch see the ONE mask of the one forward); the fake and real PatchGAN passes of the D step run as one
 batch of 2B (InstanceNorm is per sample); torch.cat never materialises.  Optionally
 (``micro_batches=2``) the batch is cut into parts that run concurrently on separate HIP streams.
+
+``step(..., valid=mask)`` keeps nodata out of the reconstruction terms: L1 and the index criteria become means over the
+pixels with ``valid != 0`` of the WHOLE batch of this rank -- one nirgan_valid_count before the micro-batches fork, then every
+micro-batch runs nirgan_pix_loss_masked with that one count as its divisor, its weights NOT multiplied by the micro-batch's share (the
+share is in the common divisor already).  The GAN terms and the D step do not see the mask.  Data parallel: each rank takes its own
+masked mean and the gradients are averaged over the ranks, as DDP would average them -- there is no global valid count, so a rank
+with few valid pixels weighs each of them more.
 """
 from __future__ import annotations
 
@@ -65,6 +72,7 @@ class _Micro:
         self.pix_ws = torch.zeros(L.PIX_LOSS_WS_ELEMS, dtype=torch.float32, device=dev)      # this micro-batch's own (streams run concurrently)
         d.ws, d.ws_elems = self.pix_ws.data_ptr(), self.pix_ws.numel()
         self.pix = d
+        self.pixm = None                  # the masked twin, made at the first step that brings a mask (_ShapeState.masked)
         # optional SSIM term (model/pix2pix.py:233-237; lambda_ssim is 0.0 in the shipped configs): runs after the pixel losses and
         # ADDS its gradient to dpred, its weighted value to losses[10]
         self.ssim = None
@@ -111,11 +119,33 @@ class _ShapeState:
         self.bucketed = tr.reducer is not None and n == 1 and OPT.dp_buckets
         self.bucketedD = self.bucketed and self.micros[0].D2.bwd_tail is not None
         self.headD = self.headG = None
+        self.valid = None                 # [B,1,H,W] mask staging of masked steps (``masked``)
         if self.bucketed:
             m = self.micros[0]
             if self.bucketedD:
                 self.headD = self._hook_tail(tr, m.D2, tr.flatD)
             self.headG = self._hook_tail(tr, m.G, tr.flatG)
+
+    def masked(self, tr: "Pix2PixTrainer"):
+        """The whole batch's mask staging tensor; at the first call also every micro-batch's nirgan_pix_loss_masked descriptor: the
+        fields of its ``pix`` with the weights of the WHOLE batch (no share: the divisor is the batch's count), its slice of the mask
+        and the trainer's one count."""
+        if self.valid is None:
+            m0 = self.micros[0]
+            B = sum(m.B for m in self.micros)
+            self.valid = torch.zeros(B, 1, m0.nir.shape[2], m0.nir.shape[3], dtype=torch.float32, device=m0.nir.device)
+            for m in self.micros:
+                d = L.PixLossMaskedDesc()
+                for name, _ in L.PixLossDesc._fields_:
+                    setattr(d, name, getattr(m.pix, name))
+                d.w_l1 = tr.lambda_l1
+                for k in RS_KEYS:
+                    w = float(tr.rs_weights.get("lambda_" + k, 0.0)) if tr.lambda_rs > 0.0 else 0.0
+                    setattr(d, "w_" + k, tr.lambda_rs * w if w > 0.0 else 0.0)
+                m.valid = self.valid[m.lo:m.hi]
+                d.valid, d.count = m.valid.data_ptr(), tr.count.data_ptr()
+                m.pixm = d
+        return self.valid
 
     @staticmethod
     def _hook_tail(tr, eng, flat):
@@ -223,6 +253,7 @@ class Pix2PixTrainer:
         if self.losses is None or rebuilt:
             # 0 D_fake 1 D_real 2 G_gan 3.. pix sums[7] 10 weighted SSIM term
             self.losses = torch.zeros(16, dtype=torch.float32, device=self.flatG.flat.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.flatG.flat.device)     # valid pixels of the batch (masked steps)
         active = getattr(self.netG, "dropout_active", None)
         self.dropout = bool(active()) if active is not None else False
         key = (B, H, W) + ((True,) if self.dropout else ())        # the active bit, as in the generator's engine pool (functional.GeneratorFn)
@@ -261,13 +292,16 @@ class Pix2PixTrainer:
         self._gan_loss(be, out + npatch * 4, npatch, True, m.scale, lp + 4, dout + npatch * 4, st)
         m.D2.backward(None, frozen=False, version=self.flatD.values_version())
 
-    def _g_pass(self, m: _Micro):
+    def _g_pass(self, m: _Micro, masked: bool = False):
         be, st = L.backend(), m.G.ctx.stream()
         lp = self.losses.data_ptr()
         m.D1.forward(parts=[(m.rgb, 0, 0), (m.G.pred, 0, 3)], version=self.flatD.values_version())
         self._gan_loss(be, m.D1.out.data_ptr(), m.n_patch, True, self.lambda_gan * m.scale, lp + 8, m.D1.dout.data_ptr(), st)
         m.D1.backward(None, frozen=True, version=self.flatD.values_version(), pred_only=True)
-        L.check(be.nirgan_pix_loss(C.byref(m.pix), st), "pix_loss")
+        if masked:
+            L.check(be.nirgan_pix_loss_masked(C.byref(m.pixm), st), "pix_loss_masked")
+        else:
+            L.check(be.nirgan_pix_loss(C.byref(m.pix), st), "pix_loss")
         if m.ssim is not None:
             L.check(be.nirgan_ssim_loss(C.byref(m.ssim), st), "ssim_loss")
         m.G.backward(None, version=self.flatG.values_version())
@@ -299,11 +333,24 @@ class Pix2PixTrainer:
             self.reducer.all_reduce_mean(flat.grad)
 
     # ------------------------------------------------------------------ one batch
-    def step(self, rgb: torch.Tensor, nir: torch.Tensor, embeds: Optional[torch.Tensor] = None) -> "LossView":
+    def step(self, rgb: torch.Tensor, nir: torch.Tensor, embeds: Optional[torch.Tensor] = None,
+             valid: Optional[torch.Tensor] = None) -> "LossView":
+        """``valid``: any [B,1,H,W] tensor, read as ``valid != 0`` (the ``"valid"`` of a scene-pool batch): L1 and the index terms are
+        then means over those pixels of the whole batch, and the gradient of a pixel left out is the GAN term alone.  With no valid
+        pixel both are 0.  Data parallel: the count is this rank's own (see the module's doc-string)."""
         B, _, H, W = rgb.shape
+        if valid is not None:
+            if self.lambda_ssim > 0.0:
+                raise NotImplementedError("valid with lambda_ssim > 0: the SSIM windows would straddle the mask")
+            if tuple(valid.shape) != (B, 1, H, W):
+                raise ValueError(f"valid {tuple(valid.shape)} must be {(B, 1, H, W)}")
         self._prepare(B, H, W)
         state = self._state
         st = self.G.ctx.stream()
+        if valid is not None:
+            staged = state.masked(self)
+            staged.copy_(valid if valid.dtype == torch.float32 else valid != 0)
+            L.check(L.backend().nirgan_valid_count(staged.data_ptr(), staged.numel(), self.count.data_ptr(), st), "valid_count")
         for m in state.micros:
             m.rgb.copy_(rgb[m.lo:m.hi])
             m.nir.copy_(nir[m.lo:m.hi])
@@ -322,34 +369,40 @@ class Pix2PixTrainer:
         self._fork(state)
         for m, s in zip(state.micros, state.streams):
             with _on_stream(s):
-                self._g_pass(m)
+                self._g_pass(m, valid is not None)
         self._join(state, self.flatG, state.extraG)
         self._reduce(state, self.flatG, state.headG)
         self.flatG.adam_step(self.lr if self.lr_g is None else self.lr_g, self.beta1, stream=st)
         self.steps += 1
-        return LossView(self, B * H * W)
+        return LossView(self, B * H * W, self.count if valid is not None else None)
 
 
 class LossView:
-    """Lazy view of the step's loss scalars (reading synchronises; the hot loop never does)."""
+    """Lazy view of the step's loss scalars (reading synchronises; the hot loop never does).  After a masked step the pixel means
+    are over the step's count of valid pixels, read from the device with the sums (``divisor``); 0 valid pixels give 0."""
 
-    def __init__(self, tr: Pix2PixTrainer, npix: int):
-        self.tr, self.npix = tr, npix
+    def __init__(self, tr: Pix2PixTrainer, npix: int, count: Optional[torch.Tensor] = None):
+        self.tr, self.npix, self.count = tr, npix, count
+
+    def divisor(self) -> int:
+        """what the pixel sums are divided by: B*H*W, or the valid count of a masked step (synchronises)"""
+        return self.npix if self.count is None else int(self.count.item())
 
     def as_dict(self) -> Dict[str, float]:
         tr = self.tr
         v = tr.losses.detach().cpu().tolist()
+        npix = max(self.divisor(), 1)
         out = {"loss_D_fake": v[0], "loss_D_real": v[1], "loss_D": v[0] + v[1]}
         gan_w = v[2]
         out["loss_G_gan"] = gan_w / tr.lambda_gan if tr.lambda_gan else 0.0
-        out["loss_G_l1"] = v[3] / self.npix
+        out["loss_G_l1"] = v[3] / npix
         loss_g = gan_w + tr.lambda_l1 * out["loss_G_l1"]
         if tr.lambda_rs > 0.0:
             rs = 0.0
             for i, k in enumerate(RS_KEYS):
                 w = float(tr.rs_weights.get("lambda_" + k, 0.0))
                 if w > 0.0:
-                    rs += w * v[4 + i] / self.npix
+                    rs += w * v[4 + i] / npix
             out["loss_G_rs"] = rs
             loss_g += tr.lambda_rs * rs
         if tr.lambda_ssim > 0.0:

@@ -37,7 +37,8 @@ class RemoteSensingIndices():
             nir_pred = nir_pred.unsqueeze(0)
         return (rgb, nir, nir_pred)
 
-    def get_and_weight_losses(self, rgb, nir, nir_pred, loss_config=None, mode="loss"):
+    def get_and_weight_losses(self, rgb, nir, nir_pred, loss_config=None, mode="loss", valid=None):
+        """``valid``: a [B,1,H,W] mask (``valid != 0``); the means then run over its pixels only (nirgan_pix_loss_masked)"""
         if loss_config is None:
             loss_config = {"lambda_ndvi": 0.333, "lambda_ndwi": 0.333, "lambda_evi": 0.333,
                            "lambda_savi": 0.0, "lambda_msavi": 0.0, "lambda_gndvi": 0.0}
@@ -47,12 +48,16 @@ class RemoteSensingIndices():
             w = [x if x > 0.0 else 0.0 for x in w]
             if not any(w):
                 return 0.0
-            return HF.PixLossFn.apply(rgb, nir, nir_pred, tuple(w), self._crit)
+            return HF.pix_loss(rgb, nir, nir_pred, tuple(w), self._crit, self._valid_4d(valid))
         elif mode == "logging_dict":
-            s = HF.index_sums(rgb, nir, nir_pred, self._crit)
+            s = HF.index_sums(rgb, nir, nir_pred, self._crit, self._valid_4d(valid))
             return {_LOG_NAMES[k]: s[1 + i] for i, k in enumerate(_ORDER)}
         else:
             raise NotImplementedError(f"Mode '{mode}' not implemented. 'loss' or 'logging_dict' are supported.")
+
+    @staticmethod
+    def _valid_4d(valid):
+        return valid.unsqueeze(0) if valid is not None and valid.dim() == 3 else valid
 
     # ------------------------------------------------------------------ single indices
     def _single(self, which, rgb, nir, nir_pred):
