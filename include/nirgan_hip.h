@@ -616,6 +616,42 @@ int64_t nirgan_tile_metrics_ws_elems(int B, int ch, int cw);
 int nirgan_tile_metrics(const nirgan_tile_metrics_desc* d, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Per-tile validation metrics over the VALID pixels of each tile: the rows of nirgan_tile_metrics under a mask.
+ * valid: [B][1][H][W] fp32, an element != 0.f is valid (-0.f is not; the convention of nirgan_pix_loss_masked / nirgan_valid_count).
+ * Per tile b, over the evaluation window (y0, x0, ch, cw):
+ *   rows[b][9]  n_valid = the number of window pixels with valid != 0
+ *   rows[b][10] n_ssim  = the number of SUPPORT-CLEAN window pixels: those whose (2r+1)^2 filter taps, r = window/2, reflected at the
+ *                         window's border like the filter itself, are all valid (the centre is a tap: n_ssim <= n_valid)
+ *   rows[b][0], [1], [4..6]  l1, l2, l1_ndvi, l1_ndwi, l1_evi: sums over the valid pixels times 1.f / n_valid
+ *   rows[b][3]  psnr from the masked l2 (+inf where that is 0).  n_valid == 0: these six columns are NaN
+ *   rows[b][2]  ssim = sum of the SSIM map over the support-clean pixels times 1.f / n_ssim (there the map has exactly its unmasked
+ *               value); n_ssim == 0: NaN
+ *   rows[b][7..8]  means of nir / pred over the valid pixels of the centred patch, NaN when the patch holds none
+ * rgb == NULL: the index columns stay untouched; patch == 0: the patch columns stay untouched; every other column is OVERWRITTEN.
+ * A dropped pixel is branched around, not multiplied by zero: NaN, +-Inf or nodata values in nir / pred / rgb at an invalid pixel reach
+ * no output.  Nothing outside the window is read, from any plane, the mask included.  Counts are exact: ch * cw <= 2^24 is required.
+ * Under a mask of ones the sums take the path of nirgan_tile_metrics (same operations, same order, 1.f / n_valid == its divisor).
+ * ws: at least the _ws_elems count of floats (11 partials per 32x32 block).  Deterministic, no atomics: a tile's row depends only on
+ * (ch, cw) and its own planes.  Argument errors: those of nirgan_tile_metrics, valid == NULL and ch * cw > 2^24, NIRGAN_ERR_ARG
+ * before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_TILE_METRIC_MASKED_COLS 11   /* the nine of NIRGAN_TILE_METRIC_COLS, n_valid, n_ssim */
+typedef struct {
+    const float* rgb;          /* [B][3][H][W] fp32 NCHW, may be NULL: index columns are then not computed */
+    const float* nir;          /* [B][1][H][W] */
+    const float* pred;         /* [B][1][H][W] */
+    int B, H, W;
+    int y0, x0, ch, cw;
+    int window; float sigma, max_val, eps;
+    int patch;
+    float* ws; int64_t ws_elems;
+    float* rows;               /* [B][NIRGAN_TILE_METRIC_MASKED_COLS] on device */
+    const float* valid;        /* [B][1][H][W] fp32, != 0.f is valid */
+} nirgan_tile_metrics_masked_desc;
+int64_t nirgan_tile_metrics_masked_ws_elems(int B, int ch, int cw);
+int nirgan_tile_metrics_masked(const nirgan_tile_metrics_masked_desc* d, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * Window statistics of a date stack: the numbers of the reference's NDVI time series (validation_utils/time_series_validation.py:
  * centroid patch means :120-132, window medians of the NDVI :243-266; per date on CPU copies there), ONE launch for the whole stack.
  * Per tile t, over the window [y0, y0+wh) x [x0, x0+ww) of the stored images:

@@ -47,6 +47,7 @@ class _PixelBaseline(_Base):
 
     hidden = None                   # nirgan_pixmlp_desc.hidden
     is_pixel_baseline = True        # nirgan_hip.fit.fit: one optimizer, no scheduler
+    masked_validation = False       # True: validation_step's scalars are over batch["valid"] (fit sets it for a run)
 
     def _setup(self, config):
         self.config = config
@@ -91,7 +92,10 @@ class _PixelBaseline(_Base):
         the device; the image / wandb logging is out of scope."""
         rgb, nir = batch["rgb"], batch["nir"]
         nir_pred = self(rgb)
-        metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val")
+        if getattr(self, "masked_validation", False):          # fit(masked_validation=True): the scalars over the batch's valid pixels
+            metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val", valid=batch.get("valid"))
+        else:
+            metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val")
         for k, v in metrics.items():
             self._log(k, v)
         return metrics["val/L1"]

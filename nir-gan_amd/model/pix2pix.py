@@ -59,6 +59,8 @@ class HipL1Loss(torch.nn.Module):
 
 
 class Px2Px_PL(_Base):
+    masked_validation = False       # True: validation_step's scalars are over batch["valid"] (nirgan_hip.fit.fit sets it for a run)
+
     def __init__(self, opt):
         super(Px2Px_PL, self).__init__()
         self.opt = opt.base_configs
@@ -191,7 +193,10 @@ class Px2Px_PL(_Base):
             rgb, nir, embeds = self.extract_batch(batch)
         nir_pred = self.predict_step(rgb, embeds) if embeds is not None else self.predict_step(rgb)
         rgb = rgb[:, :3, :, :]
-        metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val")
+        if getattr(self, "masked_validation", False):          # fit(masked_validation=True): the scalars over the batch's valid pixels
+            metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val", valid=batch.get("valid"))
+        else:
+            metrics = calculate_metrics(pred=nir_pred, target=nir, phase="val")
         for k, v in metrics.items():
             self._log(k, v)
         if self._wants_metrics() and batch_idx < self._num_val_images():

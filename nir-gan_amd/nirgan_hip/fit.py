@@ -16,10 +16,13 @@ what the reference plots from on_validation_epoch_end, model/pix2pix.py:347-412)
 (utils.logging_helpers, model/pix2pix.py:286-298) of the first ``Logging.num_val_images`` validation batches are written as PNG files.
 ``land_cover_table_path``: every validation epoch also writes the land-cover-stratified table (validation_utils.land_cover.
 evaluate_land_cover) of its validation batches to ``<stem>_e<epoch><ext>``, rank 0 under data parallel.
+``masked_validation``: the validation batches carry ``valid`` and the ``val/*`` scalars and the tile table are taken over the valid
+pixels (utils.calculate_metrics.calculate_metrics(valid=), evaluate_tiles(masked=True)).
 wandb and Lightning loggers stay out of scope.
 """
 from __future__ import annotations
 
+import math
 from types import SimpleNamespace
 from typing import Callable, Dict, Iterable, Optional
 
@@ -83,6 +86,9 @@ def _run_extras(model, val_loader, device, epoch, val_epochs, history, rank0, op
         return val_epochs % max(int(every), 1) == 0
     if opts["tile_table_path"] is not None and rank0:
         from validation_utils.tile_metrics import evaluate_tiles
+        if opts.get("masked"):
+            from functools import partial
+            evaluate_tiles = partial(evaluate_tiles, masked=True)
         _write_table(evaluate_tiles, model, val_loader, device, opts["tile_table_path"], opts["tile_table_crop"], epoch)
     if opts["land_cover_table_path"] is not None and rank0:
         from validation_utils.land_cover import evaluate_land_cover
@@ -149,7 +155,7 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
         ckpt_path: Optional[str] = None, resume_from: Optional[str] = None, tile_table_path: Optional[str] = None,
         tile_table_crop: Optional[int] = 240, time_series=None, time_series_every: int = 1,
         figures_dir: Optional[str] = None, figures_every: int = 1, land_cover_table_path: Optional[str] = None,
-        land_cover_crop: Optional[int] = 240) -> Dict[str, list]:
+        land_cover_crop: Optional[int] = 240, masked_validation: bool = False) -> Dict[str, list]:
     """Train ``model`` (model.pix2pix.Px2Px_PL, or a model.baseline_models baseline: _baseline_kind).  Returns the history
     {'train': [...], 'val': [...], 'lr': [...]}.  ``tile_table_path`` (default None: nothing changes): per validation epoch, the
     per-tile table of the validation batches as CSV, evaluated on the centred ``tile_table_crop`` window (None: whole tiles).
@@ -161,11 +167,58 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
     (rank 0 under data parallel) and the paths appended to ``history["figures"]``.  ``land_cover_table_path`` (default None: nothing
     changes): per validation epoch, the land-cover-stratified table (validation_utils.evaluate_land_cover) of the validation batches,
     which must then carry a ``mask`` of class ids, on the centred ``land_cover_crop`` window as ``<stem>_e<epoch><ext>`` (rank 0 under
-    data parallel)."""
+    data parallel).  ``masked_validation`` (default False: nothing changes): the validation batches carry ``valid``
+    (``grid_loader(.., return_valid=True)``) and the ``val/*`` scalars are those over the valid pixels of each batch
+    (``calculate_metrics(.., valid=)``; the model's ``masked_validation`` attribute is set for the run and restored), the tile table
+    of ``tile_table_path`` is the masked one, and the epoch value of each key is its mean over the batches where it is finite.  A key
+    without a finite batch is NaN, is not handed to the scheduler, and is listed in ``history["val_not_finite"]``."""
     device = device or next(model.parameters()).device
     extras = dict(tile_table_path=tile_table_path, tile_table_crop=tile_table_crop, time_series=time_series,
                   time_series_every=time_series_every, figures_dir=figures_dir, figures_every=figures_every,
-                  land_cover_table_path=land_cover_table_path, land_cover_crop=land_cover_crop)
+                  land_cover_table_path=land_cover_table_path, land_cover_crop=land_cover_crop, masked=bool(masked_validation))
+    run = (model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from, extras)
+    if not masked_validation:
+        return _fit(*run)
+    was = getattr(model, "masked_validation", False)
+    model.masked_validation = True
+    try:
+        return _fit(*run)
+    finally:
+        model.masked_validation = was
+
+
+def _val_scalars(model, val_loader, device):
+    """the epoch's ``val/*`` scalars: per key the mean over the validation batches"""
+    sums, n = {}, 0
+    for i, batch in enumerate(val_loader):
+        model.logged.clear() if hasattr(model, "logged") else None
+        model.validation_step(_to_device(batch, device), i)
+        for k, v in getattr(model, "logged", {}).items():
+            if k.startswith("val/"):
+                sums[k] = sums.get(k, 0.0) + float(v)
+        n += 1
+    return {k: _rank_mean(v / max(n, 1), device) for k, v in sums.items()}
+
+
+def _masked_val_scalars(model, val_loader, device):
+    """the epoch's ``val/*`` scalars under masked validation: per key the mean over the batches where its value is finite (a batch
+    without a valid pixel gives NaN), NaN for a key with no such batch"""
+    sums, counts = {}, {}
+    for i, batch in enumerate(val_loader):
+        model.logged.clear() if hasattr(model, "logged") else None
+        model.validation_step(_to_device(batch, device), i)
+        for k, v in getattr(model, "logged", {}).items():
+            if k.startswith("val/"):
+                sums.setdefault(k, 0.0)
+                counts.setdefault(k, 0)
+                if math.isfinite(float(v)):
+                    sums[k] += float(v)
+                    counts[k] += 1
+    return {k: _rank_mean(sums[k] / counts[k] if counts[k] else float("nan"), device) for k in sums}
+
+
+def _fit(model, train_loader, val_loader, max_epochs, device, reducer, log_every, on_log, ckpt_path, resume_from, extras):
+    time_series, figures_dir = extras["time_series"], extras["figures_dir"]
     kind = (_baseline_kind if getattr(model, "is_pixel_baseline", False) else _px2px_kind)(model, reducer)
     rank0 = reducer is None or getattr(reducer, "rank", 0) == 0
     history = {"train": [], "val": [], "lr": []}
@@ -192,20 +245,18 @@ def fit(model, train_loader: Iterable[dict], val_loader: Optional[Iterable[dict]
             step += 1
         if val_loader is not None:
             model.eval()
-            sums, n = {}, 0
-            for i, batch in enumerate(val_loader):
-                model.logged.clear() if hasattr(model, "logged") else None
-                model.validation_step(_to_device(batch, device), i)
-                for k, v in getattr(model, "logged", {}).items():
-                    if k.startswith("val/"):
-                        sums[k] = sums.get(k, 0.0) + float(v)
-                n += 1
-            val = {k: _rank_mean(v / max(n, 1), device) for k, v in sums.items()}
+            val = (_masked_val_scalars if extras["masked"] else _val_scalars)(model, val_loader, device)
             val["epoch"] = epoch
             history["val"].append(val)
             if on_log:
                 on_log(val)
-            kind.after_val(val)
+            if extras["masked"]:                             # a NaN key is not the scheduler's to see
+                lost = sorted(k for k, v in val.items() if not math.isfinite(v))
+                if lost:
+                    history.setdefault("val_not_finite", []).append({"epoch": epoch, "keys": lost})
+                kind.after_val({k: v for k, v in val.items() if k not in lost})
+            else:
+                kind.after_val(val)
             _run_extras(model, val_loader, device, epoch, val_epochs, history, rank0, extras)
             val_epochs += 1
         history["lr"].append({"epoch": epoch, **kind.lr()})

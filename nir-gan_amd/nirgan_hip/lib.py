@@ -149,6 +149,13 @@ class TileMetricsDesc(C.Structure):
                 ("ws", fp), ("ws_elems", i64), ("rows", fp)]
 
 
+TILE_METRIC_MASKED_COLS = 11    # include/nirgan_hip.h: NIRGAN_TILE_METRIC_MASKED_COLS
+
+
+class TileMetricsMaskedDesc(C.Structure):
+    _fields_ = TileMetricsDesc._fields_ + [("valid", fp)]
+
+
 WINDOW_STAT_COLS = 8            # include/nirgan_hip.h: NIRGAN_WINDOW_STAT_COLS
 
 
@@ -380,6 +387,8 @@ PROTOTYPES = {
     "nirgan_image_metrics": (i32, [C.POINTER(MetricsDesc), fp]),
     "nirgan_tile_metrics_ws_elems": (i64, [i32, i32, i32]),
     "nirgan_tile_metrics": (i32, [C.POINTER(TileMetricsDesc), fp]),
+    "nirgan_tile_metrics_masked_ws_elems": (i64, [i32, i32, i32]),
+    "nirgan_tile_metrics_masked": (i32, [C.POINTER(TileMetricsMaskedDesc), fp]),
     "nirgan_window_stats": (i32, [C.POINTER(WindowStatsDesc), fp]),
     "nirgan_val_panel_ws_bytes": (i64, [i32, i32, i32]),
     "nirgan_val_panel": (i32, [C.POINTER(ValPanelDesc), fp]),

@@ -11,6 +11,11 @@ tensor without synchronising, for callers that log asynchronously.
 (validation_utils/): one row of ``TILE_METRIC_COLUMNS`` per tile of the batch in ONE fused pass (nirgan_tile_metrics),
 the centre crop applied by indexing.
 
+``tile_metrics_masked_device(rgb, nir, pred, valid, crop, ..)`` is that table over the VALID pixels of each tile
+(nirgan_tile_metrics_masked): ``TILE_METRIC_MASKED_COLUMNS`` adds the counts ``n_valid`` and ``n_ssim``; SSIM is averaged over the
+pixels whose whole filter support is valid.  ``calculate_metrics(.., valid=mask)`` pools its rows over a batch by those counts: the
+validation scalars of a run that trains on partly valid windows (``grid_loader(.., return_valid=True)``).
+
 ``window_stats_device(rgb, nir, pred, y0, x0, wh, ww)`` gives the mean and the median of nir, pred and their NDVI over one window
 of every tile of a date stack (nirgan_window_stats): the numbers behind validation_utils/time_series_validation.py.
 
@@ -80,10 +85,33 @@ def image_metrics_device(pred: torch.Tensor, target: torch.Tensor, window_size: 
     return means
 
 
-def calculate_metrics(pred, target, phase="train"):
+def _pooled_masked_metrics(pred, target, valid, phase):
+    """the four scalars over the valid pixels of the batch: per-tile rows of tile_metrics_masked_device pooled by their counts in
+    float64 (tiles with a zero count drop out of their sum; a scalar whose total count is 0 is NaN)"""
+    if pred.dim() != 4 or pred.shape[1] != 1 or pred.shape != target.shape:
+        raise ValueError(f"calculate_metrics(valid=..) takes equal-shaped [B, 1, H, W] tensors, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    rows = tile_metrics_masked_device(None, target, pred, valid, crop=None, window_size=5, patch=0).double()
+    col = {k: rows[:, j] for j, k in enumerate(TILE_METRIC_MASKED_COLUMNS)}
+
+    def pooled(name, count):
+        keep = count > 0
+        total = count[keep].sum()
+        return ((col[name][keep] * count[keep]).sum() / total) if bool(total > 0) else rows.new_tensor(float("nan"))
+    l1, l2, ssim = (float(v) for v in torch.stack([pooled("l1", col["n_valid"]), pooled("l2", col["n_valid"]),
+                                                    pooled("ssim", col["n_ssim"])]).tolist())
+    psnr = float("nan") if math.isnan(l2) else (10.0 * math.log10(1.0 / l2) if l2 > 0.0 else float("inf"))
+    return {phase + '/L1': l1, phase + '/L2': l2, phase + '/PSNR': psnr, phase + '/SSIM': ssim}
+
+
+def calculate_metrics(pred, target, phase="train", valid=None):
     """
     Calculate PSNR, SSIM, L1 loss, and L2 loss between pred and target ([B, C, H, W]); dict of floats.
+    ``valid`` ([B, 1, H, W] or [B, H, W], != 0 is valid; pred / target [B, 1, H, W] then): the four scalars over the valid pixels
+    of the batch -- L1, L2 pooled over the tiles by ``n_valid``, SSIM (window 5) over the support-clean pixels pooled by ``n_ssim``,
+    PSNR from the pooled L2; NaN where the batch holds no such pixel.
     """
+    if valid is not None:
+        return _pooled_masked_metrics(pred, target, valid, phase)
     l1, l2, ssim = image_metrics_device(pred, target, window_size=5, max_val=1.0).tolist()
     psnr = 10.0 * math.log10(1.0 / l2) if l2 > 0.0 else float("inf")
     return {
@@ -120,6 +148,41 @@ def tile_metrics_device(rgb, nir: torch.Tensor, pred: torch.Tensor, crop=None, w
     d.window, d.sigma, d.max_val, d.eps, d.patch = int(window_size), float(sigma), float(max_val), float(eps), int(patch)
     d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
     L.check(be.nirgan_tile_metrics(C.byref(d), _stream(n.device)), "tile_metrics")
+    return rows
+
+
+# column order of nirgan_tile_metrics_masked rows (include/nirgan_hip.h)
+TILE_METRIC_MASKED_COLUMNS = TILE_METRIC_COLUMNS + ("n_valid", "n_ssim")
+assert len(TILE_METRIC_MASKED_COLUMNS) == L.TILE_METRIC_MASKED_COLS
+
+
+def tile_metrics_masked_device(rgb, nir: torch.Tensor, pred: torch.Tensor, valid: torch.Tensor, crop=None, window_size: int = 11,
+                               patch: int = 32, max_val: float = 1.0, sigma: float = 1.5, eps: float = 1e-12) -> torch.Tensor:
+    """One row of ``TILE_METRIC_MASKED_COLUMNS`` per tile over its VALID pixels: a ``B x 11`` fp32 tensor on the inputs' device, no
+    host sync (nirgan_tile_metrics_masked).
+
+    ``rgb`` / ``nir`` / ``pred`` / ``crop`` / ``patch`` as in ``tile_metrics_device``.  ``valid`` is [B, 1, H, W] or [B, H, W] of any
+    dtype on nir's device: an element ``!= 0`` is valid.  l1, l2, psnr, the index errors and the patch means are means over the valid
+    pixels of the window (``n_valid`` of them; NaN with none); ssim is the mean of the SSIM map over the ``n_ssim`` support-clean
+    pixels, those whose whole reflected filter support is valid (NaN with none).  Whatever lies in the images at an invalid pixel
+    (NaN, Inf, nodata) reaches no output."""
+    def own_checks(B, H, W):
+        if not torch.is_tensor(valid) or tuple(valid.shape) not in ((B, H, W), (B, 1, H, W)) or valid.is_complex():
+            raise ValueError(f"valid must be a [B, 1, H, W] or [B, H, W] tensor matching nir, got {tuple(getattr(valid, 'shape', ()))}")
+    c, n, p, B, H, W = _prepare(rgb, nir, pred, between=own_checks, also=(valid,))
+    v = valid.detach()
+    v = (v if v.dtype == torch.float32 else (v != 0).to(torch.float32)).reshape(B, 1, H, W).contiguous()
+    y0, x0, ch, cw = _centre_window(crop, H, W)
+    be = L.backend()
+    ws = torch.empty(int(be.nirgan_tile_metrics_masked_ws_elems(B, ch, cw)), dtype=torch.float32, device=n.device)
+    rows = torch.full((B, L.TILE_METRIC_MASKED_COLS), float("nan"), dtype=torch.float32, device=n.device)
+    d = L.TileMetricsMaskedDesc()
+    d.rgb = None if c is None else c.data_ptr()
+    d.nir, d.pred, d.valid, d.B, d.H, d.W = n.data_ptr(), p.data_ptr(), v.data_ptr(), B, H, W
+    d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
+    d.window, d.sigma, d.max_val, d.eps, d.patch = int(window_size), float(sigma), float(max_val), float(eps), int(patch)
+    d.ws, d.ws_elems, d.rows = ws.data_ptr(), ws.numel(), rows.data_ptr()
+    L.check(be.nirgan_tile_metrics_masked(C.byref(d), _stream(n.device)), "tile_metrics_masked")
     return rows
 
 

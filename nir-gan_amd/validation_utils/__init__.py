@@ -8,7 +8,7 @@ from .geo_ablation import (PolygonLayer, RasterLayer, append_info_to_df, clean_e
                            get_countries, points_in_regions, raster_lookup, read_geojson_table, write_geojson)
 from .land_cover import CLC_CLASSES, CLC_COLORS, evaluate_land_cover, summarize_land_cover  # noqa: F401
 from .plot_val_spiders import plot_radar_comparison, summarize_by  # noqa: F401
-from .tile_metrics import TABLE_KEYS, evaluate_tiles, spider_validation_callback  # noqa: F401
+from .tile_metrics import MASKED_TABLE_KEYS, TABLE_KEYS, evaluate_tiles, spider_validation_callback  # noqa: F401
 from .time_series_validation import (calculate_and_plot_timeline, get_pred_nirs_and_info, ndvi_timeline,  # noqa: F401
                                      plot_ndvi_timeline, plot_timeline)
 from .val_utils import crop_center  # noqa: F401

@@ -20,10 +20,12 @@ import os
 
 import torch
 
-from utils.calculate_metrics import TILE_METRIC_COLUMNS, tile_metrics_device
+from utils.calculate_metrics import TILE_METRIC_COLUMNS, TILE_METRIC_MASKED_COLUMNS, tile_metrics_device, tile_metrics_masked_device
 
 # the reference's metrics_dict keys in its order, then the two patch means
 TABLE_KEYS = ("id", "x", "y", "ssim", "psnr", "l1", "l2", "l1_ndvi", "l1_ndwi", "l1_evi", "patch_mean_nir", "patch_mean_pred")
+# the masked table (evaluate_tiles(masked=True)): the same columns over the valid pixels of each tile, then the two counts
+MASKED_TABLE_KEYS = TABLE_KEYS + ("n_valid", "n_ssim")
 
 
 def _items(data):
@@ -107,14 +109,19 @@ def _predicted_batches(model, data, batch_size, device=None, extras=(), who="eva
             yield (rgb, nir, coords, _predict(model, rgb, None if coords is None else coords.to(device)), *more)
 
 
-def evaluate_tiles(model, data, crop=240, batch_size=16, device=None, csv_path=None, patch=32):
+def evaluate_tiles(model, data, crop=240, batch_size=16, device=None, csv_path=None, patch=32, masked=False):
     """The validation table of ``data`` under ``model``: a dict of lists with the keys ``TABLE_KEYS``, one entry per tile.
 
     ``data``: a dataset of samples or an iterable of batches, dicts with ``rgb``, ``nir`` and optionally ``coords``
     (x = coords[0], y = coords[1]; NaN without).  ``model.predict_step(rgb, coords)`` is called in eval mode under no_grad
     (a baseline's ``predict_step(rgb)`` is accepted too) and the model's train / eval mode is restored.  ``crop``: side of the
     centred evaluation window (None: the whole tile); ``patch``: side of the centred square of the patch means, cut to the
-    window.  ``csv_path``: also write the table there in the layout of the reference's ``DataFrame.to_csv`` (row index first)."""
+    window.  ``csv_path``: also write the table there in the layout of the reference's ``DataFrame.to_csv`` (row index first).
+    ``masked=True``: every sample or batch must carry ``valid`` ([1, H, W] / [b, 1, H, W], != 0 is valid; ``KeyError`` without) and
+    the table has the keys ``MASKED_TABLE_KEYS``: every metric over the valid pixels of its tile (tile_metrics_masked_device), SSIM
+    over the pixels whose whole filter support is valid, then the counts ``n_valid`` and ``n_ssim``; a metric without pixels is NaN."""
+    if masked:
+        return _evaluate_tiles_masked(model, data, crop, batch_size, device, csv_path, patch)
     table = {k: [] for k in TABLE_KEYS}
     with contextlib.closing(_predicted_batches(model, data, batch_size, device)) as batches:
         for rgb, nir, coords, pred in batches:
@@ -129,6 +136,25 @@ def evaluate_tiles(model, data, crop=240, batch_size=16, device=None, csv_path=N
                     table[name].append(float(rows[i, j]))
     if csv_path is not None:
         write_csv(table, csv_path)
+    return table
+
+
+def _evaluate_tiles_masked(model, data, crop, batch_size, device, csv_path, patch):
+    table = {k: [] for k in MASKED_TABLE_KEYS}
+    with contextlib.closing(_predicted_batches(model, data, batch_size, device, extras=("valid",))) as batches:
+        for rgb, nir, coords, pred, valid in batches:
+            H, W = nir.shape[-2:]
+            side = min(H, W) if crop is None else int(crop)
+            rows = tile_metrics_masked_device(rgb, nir, pred, valid.to(nir.device), crop=crop, window_size=11,
+                                              patch=min(int(patch), side)).cpu()
+            for i in range(rows.shape[0]):
+                table["id"].append(len(table["id"]))
+                table["x"].append(float("nan") if coords is None else float(coords[i][0]))
+                table["y"].append(float("nan") if coords is None else float(coords[i][1]))
+                for j, name in enumerate(TILE_METRIC_MASKED_COLUMNS):
+                    table[name].append(float(rows[i, j]))
+    if csv_path is not None:
+        _write_table(table, MASKED_TABLE_KEYS, csv_path)
     return table
 
 
@@ -148,14 +174,14 @@ def write_csv(table, path):
 
 
 def spider_validation_callback(model, ds, satclip, folder="validation_utils/automated_spiders/", epoch_no=0, world=None, koppen=None,
-                               legend=None):
+                               legend=None, masked=False):
     """The reference's callback (validation_utils/spider_validation_callback.py:13): evaluates ``ds`` and writes
     ``<folder>/validation_metrics.csv``.  Without ``world`` that is all, and the table is returned.  With ``world`` (a
     ``geo_ablation.PolygonLayer``; ``koppen``: a ``RasterLayer``, ``legend``: its id -> code legend) the table is joined to the
     layers (``append_info_to_df``), its economy column cleaned (``clean_economy``) and written as
     ``<folder>/validation_metrics_ablation_satclip_<satclip>_e<epoch_no>.geojson``, the reference's name; the joined table is
-    returned."""
-    table = evaluate_tiles(model, ds, crop=240, csv_path=os.path.join(folder, "validation_metrics.csv"))
+    returned.  ``masked`` is ``evaluate_tiles``'s: the metrics over the valid pixels of each tile of a ``ds`` that carries ``valid``."""
+    table = evaluate_tiles(model, ds, crop=240, csv_path=os.path.join(folder, "validation_metrics.csv"), masked=masked)
     if world is None:
         return table
     from .geo_ablation import append_info_to_df, clean_economy, write_geojson
