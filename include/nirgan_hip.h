@@ -1588,6 +1588,51 @@ typedef struct {
 int nirgan_scene_valid(const nirgan_scene_valid_desc* d, void* stream);
 int nirgan_valid_count(const float* valid, int64_t n, int32_t* count, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Matching the histogram of a uint16 plane to a reference band (skimage.exposure.match_histograms on integer codes): a count pass,
+ * a 65 536-entry table and a lookup pass, all integer-exact.  One descriptor serves the three entries; every entry checks ITS fields
+ * before any launch and reads nothing else.  No host synchronisation, nothing is read back.
+ *
+ * A plane is n contiguous uint16 codes, 1 <= n <= 2^31-1, 2-byte aligned ONLY (a plane of a [C][H][W] view starts where it starts).
+ * A table is 8-byte aligned: hist / src_hist / ref_hist int64 [NIRGAN_SCENE_CODES], lut uint16 [NIRGAN_SCENE_CODES], totals int64 [2].
+ * With has_nodata set, `nodata` (0 .. 65535) is the code of an invalid pixel.
+ *
+ * nirgan_scene_hist       hist[v] += the number of elements of `plane` equal to v; with has_nodata, elements equal to nodata are not
+ *   counted.  The entry ADDS (64-bit integer adds, exact in any order): the caller clears the table, several planes pool into one.
+ *   One launch.
+ * nirgan_scene_match_lut  the transfer table from src_hist to ref_hist.  With
+ *     ns = sum src_hist,  nr = sum ref_hist,  cs[v] = sum_{u <= v} src_hist[u],
+ *     t_0 < .. < t_{m-1} the codes with ref_hist > 0,  q_j = (double)(sum_{u <= t_j} ref_hist[u]) / (double)nr,  x_v = (double)cs[v] / (double)ns
+ *   y_v is numpy's interp(x_v, q, t) in float64, every operation rounded on its own (no fused multiply-add):
+ *     x_v <= q_0 -> t_0;   x_v >= q_{m-1} -> t_{m-1};   else with j the last index where q_j <= x_v:
+ *     x_v == q_j -> t_j,   otherwise ((t_{j+1} - t_j) / (q_{j+1} - q_j)) * (x_v - q_j) + t_j.
+ *   The ROUNDED quantiles are compared with each other, as numpy compares them.  lut[v] = rint(y_v), ties to even, for ALL 65 536 v;
+ *   with has_nodata a result equal to nodata moves to nodata + 1 (65534 for 65535), the rule of nirgan_scene_finish: a valid pixel is
+ *   never read as nodata.  ns == 0 or nr == 0 gives the identity table lut[v] = v; the device decides this.  totals, if not NULL,
+ *   receives { ns, nr }.  Totals above 2^53 are outside the contract (the conversions to double would round).  One launch.
+ * nirgan_scene_lut_apply  out[i] = (has_nodata && plane[i] == nodata) ? nodata : lut[plane[i]].  out == plane is allowed (in place), any
+ *   other overlap of the two is refused.  One owner per element, 64-bit addressing, no atomics.  One launch.
+ *
+ * Argument errors return NIRGAN_ERR_ARG before any launch, the message names the entry: a null d or a null pointer the entry uses
+ * (totals may be NULL); n outside 1 .. 2^31-1; has_nodata with nodata outside 0 .. 65535; a plane or `out` at an odd address; a table
+ * that is not 8-byte aligned; `out` overlapping `plane` without being equal to it.
+ * ------------------------------------------------------------------------------------- */
+#define NIRGAN_SCENE_CODES 65536
+typedef struct {
+    const void* plane;                    /* device uint16 [n]: hist counts it, lut_apply reads it */
+    int64_t n;
+    int has_nodata, nodata;
+    int64_t* hist;                        /* nirgan_scene_hist: [NIRGAN_SCENE_CODES], ADDED to */
+    const int64_t* src_hist;              /* nirgan_scene_match_lut */
+    const int64_t* ref_hist;
+    int64_t* totals;                      /* [2] = { ns, nr }, or NULL */
+    uint16_t* lut;                        /* [NIRGAN_SCENE_CODES]: written by match_lut, read by lut_apply */
+    void* out;                            /* nirgan_scene_lut_apply: uint16 [n] */
+} nirgan_scene_match_desc;
+int nirgan_scene_hist(const nirgan_scene_match_desc* d, void* stream);
+int nirgan_scene_match_lut(const nirgan_scene_match_desc* d, void* stream);
+int nirgan_scene_lut_apply(const nirgan_scene_match_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

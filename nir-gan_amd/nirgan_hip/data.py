@@ -433,7 +433,8 @@ class ScenePool(_Sampler):
     def predict(self, model, s: int, **kw) -> torch.Tensor:
         """The predicted NIR band [H, W] of scene ``s``: ``nirgan_hip.inference.predict_scene`` on a view of the pool's buffer with
         the pool's first three ``bands``, its ``divisor``, ``nodata`` and the scene's geotransform row.  ``kw``: the
-        other keywords of ``predict_scene`` (tile, margin, overlap, window, batch, tta, embeds, out, scale, nodata_out)."""
+        other keywords of ``predict_scene`` (tile, margin, overlap, window, batch, tta, embeds, out, scale, nodata_out, match,
+        match_nodata)."""
         from .inference import predict_scene
         fixed = {"bands", "divisor", "nodata", "geotransform"} & set(kw)
         if fixed:
@@ -441,6 +442,21 @@ class ScenePool(_Sampler):
         view = self.scene(s)
         return predict_scene(model, view, bands=self.bands[:3], divisor=self.divisor, nodata=self.nodata,
                              geotransform=None if self.geo is None else self.geo[int(s)], **kw)
+
+    def band_histogram(self, band: int, scenes=None) -> torch.Tensor:
+        """int64 [65536]: the pooled histogram of stored band ``band`` over the named scenes (default: all) of a uint16 pool, codes
+        equal to the pool's ``nodata`` left out -- one count per scene into one table.  As ``match`` of ``predict`` it
+        matches a predicted band to the statistics of a whole set of real ones."""
+        from .inference import scene_histogram
+        if self.dtype != L.SCENE_U16:
+            raise ValueError("ScenePool.band_histogram: the pool must hold uint16 scenes")
+        if not 0 <= int(band) < self.C:
+            raise ValueError(f"band {band} outside 0 .. {self.C - 1}")
+        ids = list(range(len(self.shapes))) if scenes is None else [int(s) for s in scenes]
+        hist = torch.zeros(65536, dtype=torch.int64, device=self.device)
+        for s in ids:
+            scene_histogram(self.scene(s)[int(band)], self.nodata, hist)
+        return hist
 
     def split(self, val, guard=0) -> "PoolSplit":
         """Hold rectangles of the scenes out of training.  ``val``: ``(scene, y0, x0, h, w)`` rectangles in source pixels,

@@ -234,7 +234,7 @@ def _usable_areas(H, W, core, stride, nth, ntw):
 @torch.no_grad()
 def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None, geotransform=None, tile: int = 512, margin: int = 16,
                   overlap=None, window: str = "linear", batch: int = 8, tta: str = "none", embeds=None, out: str = "uint16", scale=None,
-                  nodata_out=None) -> torch.Tensor:
+                  nodata_out=None, match=None, match_nodata=None) -> torch.Tensor:
     """The NIR band of one device-resident scene, predicted in place -> [H, W] device tensor.
 
     ``scene``: a device tensor [C, H, W], C >= 3, contiguous: uint16 reflectance as the int16 bit patterns ``ScenePool`` stores (or
@@ -255,7 +255,13 @@ def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None
 
     ``embeds``: None calls ``model(x)``; a [1, 256] tensor gives every tile that row; ``"coords"`` (needs ``geotransform`` = (lon0,
     dlon, lat0, dlat), a sequence or a float64 device tensor) has the gather write the lon / lat of every tile's own centre and calls
-    ``model(x, model.satclip_get_inject(coords))``: each tile of a large scene gets the prior of its own location."""
+    ``model(x, model.satclip_get_inject(coords))``: each tile of a large scene gets the prior of its own location.
+
+    ``match`` (``out="uint16"`` only): a reference band -- a uint16 plane of ANY size, as ``scene_histogram`` takes it, whose
+    nodata code is ``match_nodata`` (default: ``nodata``) -- or an int64 [65536] histogram, e.g. ``ScenePool.band_histogram``.  The
+    finished plane's histogram is matched to it in place (``histogram_match_scene``) before it is returned.  With ``nodata`` given,
+    ``nodata_out`` is the reserved code: invalid pixels keep it and are not counted, valid ones never get it; without, every pixel counts
+    and no code is reserved."""
     import ctypes as C
     from . import lib as L
     k = _tta_views(tta, "predict_scene")
@@ -264,6 +270,8 @@ def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None
         raise ValueError(f"predict_scene: window must be one of {sorted(windows)}, got {window!r}")
     if out not in L.SCENE_OUT_KINDS:
         raise ValueError(f"predict_scene: out must be one of {sorted(L.SCENE_OUT_KINDS)}, got {out!r}")
+    if match is not None and out != "uint16":
+        raise ValueError(f"predict_scene: match needs out='uint16', got {out!r}")
     if isinstance(scene, np.ndarray):
         if scene.dtype not in (np.uint16, np.float32):
             raise ValueError(f"predict_scene: a numpy scene must be uint16 or float32, got {scene.dtype}")
@@ -275,6 +283,8 @@ def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None
     dev = scene.device
     if dev.type != "cuda" and not L.is_emulated():
         raise RuntimeError("predict_scene runs on MI355X (cuda tensors) only; there is no CPU path")
+    if match is not None and not _is_histogram(match):
+        match = _code_plane(match, "predict_scene: match", dev)                  # a bad reference is refused before the model runs
     Cs, H, W = (int(v) for v in scene.shape)
     is_u16 = scene.dtype != torch.float32
     bands = tuple(int(b) for b in bands)
@@ -355,7 +365,115 @@ def predict_scene(model, scene, *, bands=(0, 1, 2), divisor=10000.0, nodata=None
     d.blended, d.out_kind, d.out = acc.data_ptr(), kind, res.data_ptr()
     d.scale, d.nodata_out = float(divisor if scale is None else scale), float(nodata_out)
     L.check(be.nirgan_scene_finish(C.byref(d), st), "scene_finish")
+    if match is not None:
+        ref_nodata = nodata if match_nodata is None else match_nodata
+        histogram_match_scene(res, match, nodata=None if nodata is None else int(nodata_out), reference_nodata=ref_nodata, out=res)
     return res
+
+
+def _is_histogram(t) -> bool:
+    return torch.is_tensor(t) and t.dtype == torch.int64 and tuple(t.shape) == (65536,)
+
+
+def _code_plane(plane, who, dev=None) -> torch.Tensor:
+    """a uint16 plane ([H, W] or flat; int16 bit patterns, torch.uint16 or a numpy uint16 array) -> the same memory as a flat tensor"""
+    from . import lib as L
+    if isinstance(plane, np.ndarray):
+        if plane.dtype != np.uint16 or plane.ndim not in (1, 2):
+            raise ValueError(f"{who}: a numpy plane must be a uint16 [H, W] or flat array, got {plane.dtype} {plane.shape}")
+        plane = torch.from_numpy(np.ascontiguousarray(plane).view(np.int16)).to(dev if dev is not None else ("cpu" if L.is_emulated() else "cuda"))
+    if not torch.is_tensor(plane) or plane.dim() not in (1, 2) or plane.dtype not in (torch.int16, torch.uint16) or not plane.is_contiguous():
+        raise ValueError(f"{who}: the plane must be a contiguous [H, W] or flat tensor of int16 (uint16 bit patterns) or uint16")
+    if plane.numel() < 1:
+        raise ValueError(f"{who}: the plane is empty")
+    if plane.device.type != "cuda" and not L.is_emulated():
+        raise RuntimeError(f"{who} runs on MI355X (cuda tensors) only; there is no CPU path")
+    return plane.view(-1)
+
+
+def _match_desc(dev, nodata, who):
+    from . import lib as L
+    if nodata is not None and not 0 <= int(nodata) <= 65535:
+        raise ValueError(f"{who}: nodata {nodata} outside 0 .. 65535")
+    d = L.SceneMatchDesc()
+    d.has_nodata, d.nodata = int(nodata is not None), 0 if nodata is None else int(nodata)
+    return d, (torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None)
+
+
+def _check_histogram(h, dev, who):
+    if not _is_histogram(h) or not h.is_contiguous() or h.device != dev:
+        raise ValueError(f"{who}: a histogram is a contiguous int64 [65536] tensor on {dev}")
+    return h
+
+
+@torch.no_grad()
+def scene_histogram(plane, nodata=None, into=None) -> torch.Tensor:
+    """int64 [65536]: how often every uint16 code occurs in ``plane`` (an [H, W] or flat tensor of int16 bit patterns or uint16,
+    contiguous, possibly a view such as one band of a scene; or a numpy uint16 array, uploaded once), codes equal to ``nodata`` left
+    out (nirgan_scene_hist).  ``into``: a histogram to ADD to -- the planes of many calls pool into one -- which is
+    also what is returned."""
+    import ctypes as C
+    from . import lib as L
+    flat = _code_plane(plane, "scene_histogram", None if into is None else into.device)
+    dev = flat.device
+    hist = torch.zeros(65536, dtype=torch.int64, device=dev) if into is None else _check_histogram(into, dev, "scene_histogram: into")
+    d, st = _match_desc(dev, nodata, "scene_histogram")
+    d.plane, d.n, d.hist = flat.data_ptr(), flat.numel(), hist.data_ptr()
+    L.check(L.backend().nirgan_scene_hist(C.byref(d), st), "scene_hist")
+    return hist
+
+
+@torch.no_grad()
+def scene_match_lut(src_hist: torch.Tensor, ref_hist: torch.Tensor, nodata=None) -> torch.Tensor:
+    """The transfer table [65536] (int16 bit patterns of uint16 codes, as the pool stores them) that matches the histogram ``src_hist``
+    to ``ref_hist`` as skimage.exposure.match_histograms does, rounded to the nearest code (ties to even); a result equal to ``nodata``
+    moves to the next code.  An empty histogram on either side gives the identity (nirgan_scene_match_lut)."""
+    import ctypes as C
+    from . import lib as L
+    dev = src_hist.device if torch.is_tensor(src_hist) else None
+    _check_histogram(src_hist, dev, "scene_match_lut: src_hist")
+    _check_histogram(ref_hist, dev, "scene_match_lut: ref_hist")
+    if dev.type != "cuda" and not L.is_emulated():
+        raise RuntimeError("scene_match_lut runs on MI355X (cuda tensors) only; there is no CPU path")
+    lut = torch.empty(65536, dtype=torch.int16, device=dev)
+    d, st = _match_desc(dev, nodata, "scene_match_lut")
+    d.src_hist, d.ref_hist, d.lut = src_hist.data_ptr(), ref_hist.data_ptr(), lut.data_ptr()
+    L.check(L.backend().nirgan_scene_match_lut(C.byref(d), st), "scene_match_lut")
+    return lut
+
+
+_SAME = object()
+
+
+@torch.no_grad()
+def histogram_match_scene(plane, reference, nodata=None, reference_nodata=_SAME, out=None) -> torch.Tensor:
+    """``plane`` (as ``scene_histogram`` takes it) with its histogram matched to ``reference``: a uint16 plane of ANY size -- its own
+    pixels are counted, nothing is resampled -- or an int64 [65536] histogram.  Pixels equal to ``nodata`` are not counted and pass
+    through unchanged, no other pixel becomes ``nodata``; ``reference_nodata`` (default: ``nodata``) is the code left out of a reference
+    plane.  ``out``: where the result goes, ``out=plane`` works in place; by default a new tensor shaped like ``plane``.  Two counts, one
+    table, one lookup pass; nothing is copied to the host."""
+    import ctypes as C
+    from . import lib as L
+    flat = _code_plane(plane, "histogram_match_scene")
+    dev = flat.device
+    if torch.is_tensor(plane):
+        shaped = plane
+    else:
+        shaped = flat.view(plane.shape)
+    if _is_histogram(reference):
+        ref_hist = _check_histogram(reference, dev, "histogram_match_scene: reference")
+    else:
+        ref_hist = scene_histogram(_code_plane(reference, "histogram_match_scene: reference", dev), nodata if reference_nodata is _SAME else reference_nodata,
+                                   torch.zeros(65536, dtype=torch.int64, device=dev))
+    lut = scene_match_lut(scene_histogram(flat, nodata), ref_hist, nodata)
+    if out is None:
+        out = torch.empty_like(shaped)
+    elif not torch.is_tensor(out) or out.dtype != shaped.dtype or out.shape != shaped.shape or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"histogram_match_scene: out must be a contiguous {shaped.dtype} tensor of shape {tuple(shaped.shape)} on {dev}")
+    d, st = _match_desc(dev, nodata, "histogram_match_scene")
+    d.plane, d.n, d.lut, d.out = flat.data_ptr(), flat.numel(), lut.data_ptr(), out.data_ptr()
+    L.check(L.backend().nirgan_scene_lut_apply(C.byref(d), st), "scene_lut_apply")
+    return out
 
 
 def save_nir_npz(pred_nir: torch.Tensor, out_path: str, name: str) -> str:

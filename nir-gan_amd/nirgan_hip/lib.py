@@ -290,6 +290,14 @@ class ScenePredictDesc(C.Structure):
                 ("blended", fp), ("out_kind", i32), ("scale", f32), ("nodata_out", f32), ("out", fp)]
 
 
+SCENE_CODES = 65536                                        # include/nirgan_hip.h: NIRGAN_SCENE_CODES
+
+
+class SceneMatchDesc(C.Structure):
+    _fields_ = [("plane", fp), ("n", i64), ("has_nodata", i32), ("nodata", i32), ("hist", fp), ("src_hist", fp), ("ref_hist", fp),
+                ("totals", fp), ("lut", fp), ("out", fp)]
+
+
 class WinoDyDesc(C.Structure):
     _fields_ = [("dy", fp), ("dy_hp", i32), ("dy_wp", i32), ("dy_pad", i32), ("B", i32), ("H", i32), ("W", i32), ("K", i32),
                 ("Yt", fp), ("Yt_elems", i64), ("r", i32)]
@@ -359,6 +367,9 @@ PROTOTYPES = {
     "nirgan_scene_tile_gather": (i32, [C.POINTER(ScenePredictDesc), fp]),
     "nirgan_scene_finish": (i32, [C.POINTER(ScenePredictDesc), fp]),
     "nirgan_scene_valid": (i32, [C.POINTER(SceneValidDesc), fp]),
+    "nirgan_scene_hist": (i32, [C.POINTER(SceneMatchDesc), fp]),
+    "nirgan_scene_match_lut": (i32, [C.POINTER(SceneMatchDesc), fp]),
+    "nirgan_scene_lut_apply": (i32, [C.POINTER(SceneMatchDesc), fp]),
     "nirgan_valid_count": (i32, [fp, i64, fp, fp]),
     "nirgan_wino6_tiles": (i64, [i32, i32, i32]),
     "nirgan_wino6_tiles_r": (i64, [i32, i32, i32, i32]),
